@@ -9,10 +9,18 @@ total work is fixed: "scaling": "strong".
 
 A step = one full Q1 pipeline pass over the HBM-resident shard
 (generation/upload excluded — inputs resident before the timed region).
-The line also carries an untimed "extra" with Q3 (configs[2]/[3])
-measured the same way outside the main timed region.
 
-Run:  python bench.py --gpus N --steps K --warmup W
+A plain run sets up, warms up, times the K steps and prints the result
+line; nothing else runs.  --dump-outputs DIR also writes what the last
+timed step returned (the Q1 group rows) as .npy files, so two builds
+can be compared output for output: the inputs are seeded and identical
+from run to run.  --full adds everything measured outside the timed
+region: the untimed "extra" with Q3 (configs[2]/[3]), Q5 and the
+generic-plan Q6 measured the same way, and the CPU baseline legs
+(--skip-q3 / --skip-cpu-baseline drop either from a --full run).
+
+Run:  python bench.py --gpus N --steps K --warmup W [--full]
+                      [--dump-outputs DIR]
 (N>1 via torch.distributed.run; RANK/LOCAL_RANK/WORLD_SIZE honored.)
 """
 import argparse
@@ -141,6 +149,41 @@ def annotate_stats(stats, calib):
     return stats
 
 
+Q1_DUMP_COLS = ("returnflag", "linestatus", "count", "sum_qty_c",
+                "sum_base_c", "sum_dcol_c", "sum_disc4", "sum_charge6")
+
+
+def dump_q1_outputs(dirpath, groups):
+    """Write the Q1 group rows execute_q1 returned (the last timed
+    step's) under dirpath, float64:
+
+    q1_groups.npy         (n_groups, 8), columns Q1_DUMP_COLS; the two
+                          key chars as code points, the integer
+                          aggregates rounded to the nearest double (the
+                          128-bit decimal sums exceed 2^53 at SF100).
+    q1_groups_limbs32.npy (n_groups, 6, 4): the six integer aggregates
+                          (Q1_DUMP_COLS[2:]) exactly, as the four 32-bit
+                          limbs, least significant first, of their
+                          128-bit two's complement.
+    """
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    vals = np.zeros((len(groups), len(Q1_DUMP_COLS)), dtype=np.float64)
+    limbs = np.zeros((len(groups), len(Q1_DUMP_COLS) - 2, 4),
+                     dtype=np.float64)
+    for i, g in enumerate(groups):
+        vals[i, 0] = ord(g["returnflag"])
+        vals[i, 1] = ord(g["linestatus"])
+        for j, key in enumerate(Q1_DUMP_COLS[2:]):
+            vals[i, 2 + j] = float(g[key])
+            u = g[key] & ((1 << 128) - 1)
+            for k in range(4):
+                limbs[i, j, k] = (u >> (32 * k)) & 0xFFFFFFFF
+    np.save(os.path.join(dirpath, "q1_groups.npy"), vals)
+    np.save(os.path.join(dirpath, "q1_groups_limbs32.npy"), limbs)
+
+
 def main():
     global SF
     ap = argparse.ArgumentParser()
@@ -149,9 +192,21 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--sf", type=int, default=SF)
-    ap.add_argument("--skip-q3", action="store_true")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the untimed extras (Q3/Q5/Q6) and "
+                         "the CPU baseline legs after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's Q1 result rows as "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--skip-q3", action="store_true",
+                    help="with --full: leave out the Q3/Q5/Q6 extras")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave out the CPU baseline legs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     SF = args.sf
 
     import torch
@@ -251,9 +306,12 @@ def main():
         roofline["achieved_rocprof"] = algo_bytes / (rp / 1000.0) / 1e9
         roofline["frac_rocprof"] = roofline["achieved_rocprof"] / peak
 
+    if rank == 0 and args.dump_outputs:
+        dump_q1_outputs(args.dump_outputs, res_q1)
+
     extra = {}
     try:
-      if not args.skip_q3:
+      if args.full and not args.skip_q3:
         log("[bench] Q3/Q5 extra (untimed region)...")
         od = eng.register_synth("orders", seed=SEED, sf=SF)
         cu = eng.register_synth("customer", seed=SEED, sf=SF)
@@ -350,7 +408,7 @@ def main():
         extra["error"] = repr(exc)
 
     cpu_baseline = None
-    if rank == 0 and n == 1 and not args.skip_cpu_baseline:
+    if rank == 0 and n == 1 and args.full and not args.skip_cpu_baseline:
         log("[bench] CPU baseline (oracle, bounded sample)...")
         cpu_baseline = cpu_baseline_leg(cutoff_q1)
 

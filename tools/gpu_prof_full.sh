@@ -1,11 +1,13 @@
 #!/bin/bash
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/bench_out}
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-R=$GRAFT_REPO_ROOT
 cd $R
-{ timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_full -- \
-    python bench.py --steps 3 --warmup 1 --skip-cpu-baseline;
-  echo "TRACE_RC=$?"; } > gpurun_out/prof_full.log 2>&1
-{ timeout 300 rocprofv3 --kernel-trace -d $R/gpurun_out/prof_sort -- \
+{ timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_full -- \
+    python bench.py --full --steps 3 --warmup 1 --skip-cpu-baseline;
+  echo "TRACE_RC=$?"; } > $OUT/prof_full.log 2>&1
+{ timeout 300 rocprofv3 --kernel-trace -d $OUT/prof_sort -- \
     python -m pytest tests/test_gpu_sort.py -m gpu -q;
-  echo "SORT_RC=$?"; } >> gpurun_out/prof_full.log 2>&1
-grep -E "RC=" gpurun_out/prof_full.log
+  echo "SORT_RC=$?"; } >> $OUT/prof_full.log 2>&1
+grep -E "RC=" $OUT/prof_full.log

@@ -1,14 +1,17 @@
 #!/bin/bash
-cd /root/repo
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/bench_out}
+mkdir -p "$OUT"
+cd $R
 { for sf in 200 500; do
     echo "=== SF$sf ==="
-    timeout 500 python bench.py --sf $sf --steps 2 --warmup 1 --skip-cpu-baseline 2>&1 | grep -E '^\{"metric"' 
+    timeout 500 python bench.py --full --sf $sf --steps 2 --warmup 1 --skip-cpu-baseline 2>&1 | grep -E '^\{"metric"'
     echo "RC=$?"
   done
-} > gpurun_out/sf_sweep.log 2>&1
-python3 - <<'PY'
-import json
-for l in open('gpurun_out/sf_sweep.log'):
+} > $OUT/sf_sweep.log 2>&1
+OUT=$OUT python3 - <<'PY'
+import json, os
+for l in open(os.environ['OUT'] + '/sf_sweep.log'):
     l=l.strip()
     if l.startswith('==') or l.startswith('RC'):
         print(l)

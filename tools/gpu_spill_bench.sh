@@ -1,6 +1,9 @@
 #!/bin/bash
-cd /root/repo
-GG_SPILL_DEBUG=1 timeout 800 python - <<'PY' > gpurun_out/spill_bench.log 2>&1
+R=$(cd "$(dirname "$0")/.." && pwd)
+OUT=${OUT:-$R/bench_out}
+mkdir -p "$OUT"
+cd $R
+GG_SPILL_DEBUG=1 timeout 800 python - <<'PY' > $OUT/spill_bench.log 2>&1
 import sys, time
 sys.path.insert(0, ".")
 import numpy as np
@@ -29,4 +32,4 @@ assert np.array_equal(k1, k2) and np.array_equal(s1, s2) and np.array_equal(c1, 
 print("spill == in-memory on 50M subset: OK")
 eng.shutdown()
 PY
-tail -16 gpurun_out/spill_bench.log
+tail -16 $OUT/spill_bench.log
