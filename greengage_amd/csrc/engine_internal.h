@@ -586,9 +586,17 @@ struct PlanJoinDev
 	uint64_t hslots;
 };
 
+/* One device accumulator slot (two u64 words).  kind 0..2 are the
+ * descriptor's COUNT(*) / COUNT(factors non-NULL) / SUM; plan.cpp
+ * lowers MIN, MAX and AVG onto these plus two order-encoded kinds:
+ *   3 = MIN word: ~(x ^ 0x8000000000000000)   } combined by UNSIGNED
+ *   4 = MAX word:   x ^ 0x8000000000000000    } max; word 1 unused
+ * Zero is the identity of both, so zero-initialised tables and the
+ * skip-zero flushes need no special case; the paired count slot tells
+ * "no input" from a real INT64_MAX / INT64_MIN. */
 struct PlanAggDev
 {
-	int kind;		/* gg_plan_aggkind */
+	int kind;		/* 0..4, see above */
 	int nf;
 	const void *col[3];
 	const uint8_t *nulls[3];

@@ -55,6 +55,19 @@ struct PlanResolved
 	 * and gets baked into a direct-indexed kernel */
 	std::shared_ptr<void> rtc_baked;
 	bool bake_tried = false;
+	/* descriptor aggregates in order, lowered onto the device
+	 * accumulator slots dev.aggs[] (engine_internal.h PlanAggDev):
+	 * MIN/MAX = encoded value word + non-NULL count, AVG = SUM +
+	 * count; the helper counts are shared between aggregates over
+	 * the same factor columns */
+	struct OutAgg
+	{
+		int kind;	/* gg_plan_aggkind */
+		int slot;	/* value / sum accumulator */
+		int cnt;	/* helper count accumulator, or -1 */
+	};
+	std::vector<OutAgg> outs;
+	int out_slots = 0;	/* 16-byte arena slots per result row */
 };
 
 static int coltype_width(gg_coltype t)
@@ -180,23 +193,27 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		R->pred_bytes_per_row += R->dev.gwidth[g];
 	}
 
-	R->dev.naggs = d->naggs;
+	int nacc = 0;
+	std::vector<int> helpers;	/* helper count slots so far */
+
 	for (int a = 0; a < d->naggs; a++)
 	{
 		const gg_plan_agg *A = &d->aggs[a];
-		PlanAggDev *D = &R->dev.aggs[a];
+		PlanAggDev T;
 
-		if (A->kind < 0 || A->kind > 2)
+		std::memset(&T, 0, sizeof(T));
+		if (A->kind < 0 || A->kind > GG_AGG_AVG)
 			return fail(GG_ENOTSUP, "plan: agg %d kind", a);
 		if (A->kind == GG_AGG_COUNT_STAR)
-			D->nf = 0;
+			T.nf = 0;
 		else if (A->nfactors < 1 || A->nfactors > 3 ||
-			 (A->kind == GG_AGG_COUNT_COL && A->nfactors != 1))
+			 ((A->kind == GG_AGG_COUNT_COL ||
+			   A->kind == GG_AGG_MIN || A->kind == GG_AGG_MAX) &&
+			  A->nfactors != 1))
 			return fail(GG_ENOTSUP, "plan: agg %d factors", a);
 		else
-			D->nf = A->nfactors;
-		D->kind = A->kind;
-		for (int f = 0; f < D->nf; f++)
+			T.nf = A->nfactors;
+		for (int f = 0; f < T.nf; f++)
 		{
 			Table::Col *c = scan->find(A->col[f] ? A->col[f]
 						   : "");
@@ -207,13 +224,57 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 			if (A->mod[f] < 0 || A->mod[f] > 2)
 				return fail(GG_ENOTSUP,
 					    "plan: agg %d factor mod", a);
-			D->col[f] = c->dev;
-			D->nulls[f] = (const uint8_t *) c->nulls;
-			D->width[f] = coltype_width(c->type);
-			D->mod[f] = A->mod[f];
-			R->pred_bytes_per_row += D->width[f];
+			T.col[f] = c->dev;
+			T.nulls[f] = (const uint8_t *) c->nulls;
+			T.width[f] = coltype_width(c->type);
+			T.mod[f] = A->mod[f];
+			R->pred_bytes_per_row += T.width[f];
 		}
+
+		/* lower onto accumulator slots; helper slots re-read the
+		 * factors' NULL flags only, so they add nothing to
+		 * pred_bytes_per_row */
+		auto push = [&](int devkind) -> int
+		{
+			if (nacc >= GG_PLAN_MAX_AGGS)
+				return -1;
+			R->dev.aggs[nacc] = T;
+			R->dev.aggs[nacc].kind = devkind;
+			return nacc++;
+		};
+		PlanResolved::OutAgg O{A->kind, -1, -1};
+
+		if (A->kind <= GG_AGG_SUM)
+			O.slot = push(A->kind);
+		else
+		{
+			O.slot = push(A->kind == GG_AGG_MIN ? 3
+				      : A->kind == GG_AGG_MAX ? 4 : GG_AGG_SUM);
+			for (int h : helpers)
+			{
+				const PlanAggDev &H = R->dev.aggs[h];
+				bool same = H.nf == T.nf;
+
+				for (int f = 0; same && f < T.nf; f++)
+					same = H.col[f] == T.col[f];
+				if (same)
+					O.cnt = h;
+			}
+			if (O.cnt < 0 && O.slot >= 0)
+			{
+				O.cnt = push(GG_AGG_COUNT_COL);
+				helpers.push_back(O.cnt);
+			}
+		}
+		if (O.slot < 0 || (A->kind > GG_AGG_SUM && O.cnt < 0))
+			return fail(GG_ENOTSUP,
+				    "plan: aggregates need more than %d "
+				    "accumulator slots (MIN/MAX/AVG take two)",
+				    GG_PLAN_MAX_AGGS);
+		R->outs.push_back(O);
+		R->out_slots += A->kind == GG_AGG_AVG ? 2 : 1;
 	}
+	R->dev.naggs = nacc;
 
 	Pipeline *p = new Pipeline();
 
@@ -504,11 +565,19 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 					if (acc.empty())
 						acc.assign(naggs, 0);
 					for (int a = 0; a < naggs; a++)
-						acc[a] += ((i128)
-							   (int64_t)
-							   row[2 + 2 * a]
-							   << 64) |
+					{
+						i128 v = ((i128) (int64_t)
+							  row[2 + 2 * a] << 64) |
 							(i128) row[1 + 2 * a];
+
+						/* encoded MIN/MAX words merge by
+						 * unsigned max (0 = no input),
+						 * everything else by addition */
+						if (R->dev.aggs[a].kind >= 3)
+							acc[a] = std::max(acc[a], v);
+						else
+							acc[a] += v;
+					}
 				}
 			rows.clear();
 			for (auto &kv : merged)
@@ -561,7 +630,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		return a0 != b0 ? a0 < b0 : a1 < b1;
 	});
 
-	size_t need = 16 + (size_t) ng * (16 + 16 * (size_t) naggs);
+	size_t need = 16 + (size_t) ng * (16 + 16 * (size_t) R->out_slots);
 
 	if (bytes < need)
 		return fail(GG_EINVAL, "plan arena too small (%zu < %zu)",
@@ -569,7 +638,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	{
 		uint8_t *w = (uint8_t *) arena;
 		int64_t ng64 = (int64_t) ng;
-		int32_t na32 = naggs, ngc32 = R->dev.ngroup;
+		int32_t na32 = R->out_slots, ngc32 = R->dev.ngroup;
 
 		std::memcpy(w, &ng64, 8);
 		std::memcpy(w + 8, &na32, 4);
@@ -584,9 +653,35 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			std::memcpy(w, &k0, 8);
 			std::memcpy(w + 8, &k1, 8);
 			w += 16;
-			std::memcpy(w, &rows[i * rowsz + 1],
-				    16 * (size_t) naggs);
-			w += 16 * (size_t) naggs;
+			for (const PlanResolved::OutAgg &O : R->outs)
+			{
+				const unsigned long long *v =
+					&rows[i * rowsz + 1 + 2 * O.slot];
+				unsigned long long cell[2] = {v[0], v[1]};
+
+				if (O.kind == GG_AGG_MIN || O.kind == GG_AGG_MAX)
+				{
+					/* decode the order-encoded word; N = 0
+					 * is SQL NULL (lo = 0) */
+					unsigned long long n =
+						rows[i * rowsz + 1 + 2 * O.cnt];
+					unsigned long long e =
+						O.kind == GG_AGG_MIN ? ~v[0] : v[0];
+
+					cell[0] = n ? e ^ 0x8000000000000000ull
+						: 0;
+					cell[1] = n;
+				}
+				std::memcpy(w, cell, 16);
+				w += 16;
+				if (O.kind == GG_AGG_AVG)
+				{
+					cell[0] = rows[i * rowsz + 1 + 2 * O.cnt];
+					cell[1] = 0;
+					std::memcpy(w, cell, 16);
+					w += 16;
+				}
+			}
 		}
 	}
 	*written = need;
@@ -635,8 +730,13 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 					const PlanAggDev &A = R->dev.aggs[a];
 					long double lo = 1.0L, hi = 1.0L;
 
+					/* counts add [1,1]; MIN/MAX words
+					 * combine by max over a full u64
+					 * word and take no part in the
+					 * additive bound; an AVG's sum is
+					 * a kind-2 slot like any SUM */
 					if (A.kind != 2)
-						continue;	/* count: [1,1] */
+						continue;
 					for (int f = 0;
 					     fastok && f < A.nf; f++)
 					{

@@ -322,7 +322,7 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 
 	/* pass 1: one load per distinct (pointer, width) */
 	for (int a = 0; a < D.naggs; a++)
-		if (D.aggs[a].kind == 2)
+		if (D.aggs[a].kind >= 2)
 			for (int f = 0; f < D.aggs[a].nf; f++)
 				(void) var_of(a, f);
 	/* pass 1b: each distinct (var, 100±) term once — (100-disc)
@@ -331,7 +331,7 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		std::vector<std::pair<int, int>> mods_done;
 
 		for (int a = 0; a < D.naggs; a++)
-			if (D.aggs[a].kind == 2)
+			if (D.aggs[a].kind >= 2)
 				for (int f = 0; f < D.aggs[a].nf; f++)
 				{
 					int m = D.aggs[a].mod[f];
@@ -381,6 +381,26 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 			aggfn += buf;
 			continue;
 		}
+		if (D.aggs[a].kind >= 3)
+		{
+			/* MIN/MAX word: order-encode AFTER the modifier so
+			 * unsigned max combines both (MAX: x ^ msb, MIN:
+			 * its complement; 0 = identity = "no input") */
+			int u = var_of(a, 0);
+			char x[32];
+
+			if (D.aggs[a].mod[0])
+				std::snprintf(x, sizeof(x), "xm%d_%d", u,
+					      (int) D.aggs[a].mod[0]);
+			else
+				std::snprintf(x, sizeof(x), "xu%d", u);
+			std::snprintf(buf, sizeof(buf),
+				      "\t\tav[%d] = (VAT) %s((unsigned long long) %s"
+				      " ^ 0x8000000000000000ull);\n",
+				      a, D.aggs[a].kind == 3 ? "~" : "", x);
+			aggfn += buf;
+			continue;
+		}
 		std::snprintf(buf, sizeof(buf), "\t\t{ VAT v = 1;\n");
 		aggfn += buf;
 		for (int f = 0; f < D.aggs[a].nf; f++)
@@ -402,6 +422,100 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	aggfn += "\t};\n";
 	s += aggfn;
 
+	/* Per-aggregate transition code, emitted only for plans holding a
+	 * MIN/MAX word.  The kinds are known here, so each accumulator gets
+	 * its own add or max and the row loop carries no kind branch.
+	 * Plans without such a word keep the uniform add loops below, so
+	 * their generated source does not change. */
+	bool has_mm = false;
+
+	for (int a = 0; a < D.naggs; a++)
+		if (D.aggs[a].kind >= 3)
+			has_mm = true;
+	/* av[a] into the accumulator at lo (and hi: empty = one-word
+	 * fast tier); MIN/MAX words use the non-returning unsigned max */
+	auto emit_atomic = [&](std::string &o, const char *ind, int a,
+			       const std::string &lo, const std::string &hi)
+	{
+		char b[1024];
+
+		if (D.aggs[a].kind >= 3)
+			std::snprintf(b, sizeof(b),
+				      "%sif (AOK(%d))\n%s\tatomicMax(&%s, "
+				      "(unsigned long long) av[%d]);\n",
+				      ind, a, ind, lo.c_str(), a);
+		else if (hi.empty())
+			std::snprintf(b, sizeof(b),
+				      "%sif (AOK(%d))\n%s\tatomicAdd(&%s, "
+				      "(unsigned long long) av[%d]);\n",
+				      ind, a, ind, lo.c_str(), a);
+		else
+			std::snprintf(b, sizeof(b),
+				      "%sif (AOK(%d))\n%s{\n"
+				      "%s\tunsigned long long vlo = (unsigned long long) av[%d];\n"
+				      "%s\tunsigned long long vhi = (unsigned long long) (av[%d] >> 64);\n"
+				      "%s\tunsigned long long old = atomicAdd(&%s, vlo);\n\n"
+				      "%s\tif (old + vlo < old)\n%s\t\tvhi++;\n"
+				      "%s\tif (vhi)\n%s\t\tatomicAdd(&%s, vhi);\n%s}\n",
+				      ind, a, ind, ind, a, ind, a, ind,
+				      lo.c_str(), ind, ind, ind, ind,
+				      hi.c_str(), ind);
+		o += b;
+	};
+	/* fold the LREPL replicas of accumulator a (words w0/w1 indexed by
+	 * rr; w1 empty = one-word tier) into the global slot `slot` */
+	auto emit_flush = [&](std::string &o, int a, const std::string &w0,
+			      const std::string &w1)
+	{
+		char b[1536];
+
+		if (D.aggs[a].kind >= 3)
+			std::snprintf(b, sizeof(b),
+				      "\t\t{\n\t\t\tunsigned long long m = 0;\n\n"
+				      "\t\t\tfor (int rr = 0; rr < LREPL; rr++)\n"
+				      "\t\t\t\tif (%s > m)\n\t\t\t\t\tm = %s;\n"
+				      "\t\t\tif (m)\n"
+				      "\t\t\t\tatomicMax(&P.tvals[(slot * NA + %d) * 2], m);\n"
+				      "\t\t}\n",
+				      w0.c_str(), w0.c_str(), a);
+		else
+		{
+			char fold[512];
+
+			if (w1.empty())
+				std::snprintf(fold, sizeof(fold),
+					      "\t\t\t\tlo += %s;\n", w0.c_str());
+			else
+				std::snprintf(fold, sizeof(fold),
+					      "\t\t\t{\n"
+					      "\t\t\t\tunsigned long long rl = %s;\n"
+					      "\t\t\t\tunsigned long long o = lo;\n\n"
+					      "\t\t\t\tlo += rl;\n"
+					      "\t\t\t\thi += %s + (lo < o);\n"
+					      "\t\t\t}\n",
+					      w0.c_str(), w1.c_str());
+			std::snprintf(b, sizeof(b),
+				      "\t\t{\n\t\t\tunsigned long long lo = 0, hi = 0;\n\n"
+				      "\t\t\tfor (int rr = 0; rr < LREPL; rr++)\n%s"
+				      "\t\t\tif (lo || hi)\n\t\t\t{\n"
+				      "\t\t\t\tunsigned long long old =\n"
+				      "\t\t\t\t\tatomicAdd(&P.tvals[(slot * NA + %d) * 2], lo);\n\n"
+				      "\t\t\t\tif (old + lo < old)\n\t\t\t\t\thi++;\n"
+				      "\t\t\t\tif (hi)\n"
+				      "\t\t\t\t\tatomicAdd(&P.tvals[(slot * NA + %d) * 2 + 1], hi);\n"
+				      "\t\t\t}\n\t\t}\n",
+				      fold, a, a);
+		}
+		o += b;
+	};
+	auto idx = [](const char *fmt, int a) -> std::string
+	{
+		char b[128];
+
+		std::snprintf(b, sizeof(b), fmt, a);
+		return b;
+	};
+
 	/* NAGGS as a real constant for array bounds */
 	s += std::string("\tconstexpr int NA = ") +
 		std::to_string(D.naggs) + ";\n";
@@ -421,7 +535,27 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		bool aok[NA];
 
 		agg_vals(i, av, aok);
-		for (int a = 0; a < NA; a++)
+)GG";
+		if (has_mm)
+			for (int a = 0; a < D.naggs; a++)
+			{
+				if (D.aggs[a].kind >= 3)
+					std::snprintf(buf, sizeof(buf),
+						      "\t\tif (AOK(%d) && (unsigned long long) av[%d] > alo[%d])\n"
+						      "\t\t\talo[%d] = (unsigned long long) av[%d];\n",
+						      a, a, a, a, a);
+				else
+					std::snprintf(buf, sizeof(buf),
+						      "\t\tif (AOK(%d))\n\t\t{\n"
+						      "\t\t\tunsigned long long old = alo[%d];\n\n"
+						      "\t\t\talo[%d] += (unsigned long long) av[%d];\n"
+						      "\t\t\tahi[%d] += (long long) (av[%d] >> 64) + (alo[%d] < old);\n"
+						      "\t\t}\n",
+						      a, a, a, a, a, a, a);
+				s += buf;
+			}
+		else
+			s += R"GG(		for (int a = 0; a < NA; a++)
 		{
 			if (!AOK(a))
 				continue;
@@ -431,8 +565,44 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 			alo[a] += vlo;
 			ahi[a] += (long long) (av[a] >> 64) + (alo[a] < old);
 		}
-	}
-	for (int a = 0; a < NA; a++)
+)GG";
+		s += "\t}\n";
+		if (has_mm)
+			for (int a = 0; a < D.naggs; a++)
+			{
+				char rb[1024];
+
+				/* MIN/MAX word: wave max, one global max per
+				 * wave; the rest: wave add as in the uniform
+				 * loop */
+				if (D.aggs[a].kind >= 3)
+					std::snprintf(rb, sizeof(rb),
+						      "\tfor (int off = 32; off; off >>= 1)\n\t{\n"
+						      "\t\tunsigned long long o = __shfl_down(alo[%d], off, 64);\n\n"
+						      "\t\tif (o > alo[%d])\n\t\t\talo[%d] = o;\n\t}\n"
+						      "\tif ((threadIdx.x & 63) == 0 && alo[%d])\n"
+						      "\t\tatomicMax(&P.tvals[2 * %d], alo[%d]);\n",
+						      a, a, a, a, a, a);
+				else
+					std::snprintf(rb, sizeof(rb),
+						      "\tfor (int off = 32; off; off >>= 1)\n\t{\n"
+						      "\t\tunsigned long long olo = alo[%d];\n\n"
+						      "\t\talo[%d] += __shfl_down(alo[%d], off, 64);\n"
+						      "\t\tahi[%d] += __shfl_down(ahi[%d], off, 64) +\n"
+						      "\t\t\t(long long) (alo[%d] < olo);\n\t}\n"
+						      "\tif ((threadIdx.x & 63) == 0 && (alo[%d] || ahi[%d]))\n\t{\n"
+						      "\t\tunsigned long long old =\n"
+						      "\t\t\tatomicAdd(&P.tvals[2 * %d], alo[%d]);\n"
+						      "\t\tunsigned long long hi = (unsigned long long) ahi[%d] +\n"
+						      "\t\t\t(old + alo[%d] < old ? 1ull : 0ull);\n\n"
+						      "\t\tif (hi)\n"
+						      "\t\t\tatomicAdd(&P.tvals[2 * %d + 1], hi);\n\t}\n",
+						      a, a, a, a, a, a, a, a, a, a,
+						      a, a, a);
+				s += rb;
+			}
+		else
+			s += R"GG(	for (int a = 0; a < NA; a++)
 	{
 		for (int off = 32; off; off >>= 1)
 		{
@@ -453,7 +623,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 				atomicAdd(&P.tvals[2 * a + 1], hi);
 		}
 	}
-	if (blockIdx.x == 0 && threadIdx.x == 0)
+)GG";
+		s += R"GG(	if (blockIdx.x == 0 && threadIdx.x == 0)
 		P.tkeys[0] = 0;
 }
 )GG";
@@ -594,7 +765,17 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 			unsigned long long *mine = &lvals[lrep * LPAD];
 
 			tmask |= 1u << g;
-			for (int a = 0; a < NA; a++)
+)GG";
+			if (has_mm)
+				for (int a = 0; a < D.naggs; a++)
+					emit_atomic(s, "\t\t\t", a,
+						    idx(fast ? "mine[g * NA + %d]"
+							: "mine[(g * NA + %d) * 2]", a),
+						    fast ? std::string()
+						    : idx("mine[(g * NA + %d) * 2 + 1]",
+							  a));
+			else
+				s += R"GG(			for (int a = 0; a < NA; a++)
 			{
 				if (!AOK(a))
 					continue;
@@ -616,7 +797,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 						  vhi);
 #endif
 			}
-		}
+)GG";
+			s += R"GG(		}
 		else
 			/* a code outside the baked set is impossible on
 			 * re-execution over immutable tables; if it ever
@@ -638,7 +820,17 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		int64_t slot = gslot(GC[q]);
 
 		if (slot < 0) { atomicOr(P.err, 1ull); continue; }
-		for (int a = 0; a < NA; a++)
+)GG";
+			if (has_mm)
+				for (int a = 0; a < D.naggs; a++)
+					emit_flush(s, a,
+						   idx(fast ? "lvals[rr * LPAD + q * NA + %d]"
+						       : "lvals[rr * LPAD + (q * NA + %d) * 2]", a),
+						   fast ? std::string()
+						   : idx("lvals[rr * LPAD + (q * NA + %d) * 2 + 1]",
+							 a));
+			else
+				s += R"GG(		for (int a = 0; a < NA; a++)
 		{
 #if LW == 1
 			unsigned long long lo = 0, hi = 0;
@@ -670,7 +862,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 				atomicAdd(&P.tvals[(slot * NA + a) * 2 + 1],
 					  hi);
 		}
-	}
+)GG";
+			s += R"GG(	}
 }
 )GG";
 			goto compile;
@@ -748,7 +941,14 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		}
 		if (ls >= 0)
 		{
-			for (int a = 0; a < NA; a++)
+)GG";
+		if (has_mm)
+			for (int a = 0; a < D.naggs; a++)
+				emit_atomic(s, "\t\t\t", a,
+					    idx("lvals[lrep][ls][2 * %d]", a),
+					    idx("lvals[lrep][ls][2 * %d + 1]", a));
+		else
+			s += R"GG(			for (int a = 0; a < NA; a++)
 			{
 				if (!AOK(a))
 					continue;
@@ -765,13 +965,22 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 					atomicAdd(&lvals[lrep][ls][2 * a + 1],
 						  vhi);
 			}
-		}
+)GG";
+		s += R"GG(		}
 		else
 		{
 			int64_t slot = gslot(code);
 
 			if (slot < 0) { atomicOr(P.err, 1ull); continue; }
-			for (int a = 0; a < NA; a++)
+)GG";
+		if (has_mm)
+			for (int a = 0; a < D.naggs; a++)
+				emit_atomic(s, "\t\t\t", a,
+					    idx("P.tvals[(slot * NA + %d) * 2]", a),
+					    idx("P.tvals[(slot * NA + %d) * 2 + 1]",
+						a));
+		else
+			s += R"GG(			for (int a = 0; a < NA; a++)
 			{
 				if (!AOK(a))
 					continue;
@@ -788,7 +997,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 					atomicAdd(&P.tvals[(slot * NA + a) * 2 + 1],
 						  vhi);
 			}
-		}
+)GG";
+		s += R"GG(		}
 	}
 	__syncthreads();
 	for (int q = threadIdx.x; q < LSLOTS; q += blockDim.x)
@@ -798,7 +1008,13 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		int64_t slot = gslot(lkeys[q]);
 
 		if (slot < 0) { atomicOr(P.err, 1ull); continue; }
-		for (int a = 0; a < NA; a++)
+)GG";
+		if (has_mm)
+			for (int a = 0; a < D.naggs; a++)
+				emit_flush(s, a, idx("lvals[rr][q][2 * %d]", a),
+					   idx("lvals[rr][q][2 * %d + 1]", a));
+		else
+			s += R"GG(		for (int a = 0; a < NA; a++)
 		{
 			unsigned long long lo = 0, hi = 0;
 
@@ -821,7 +1037,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 				atomicAdd(&P.tvals[(slot * NA + a) * 2 + 1],
 					  hi);
 		}
-	}
+)GG";
+		s += R"GG(	}
 }
 )GG";
 	}

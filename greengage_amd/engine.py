@@ -71,6 +71,9 @@ class _PlanDesc(ctypes.Structure):
 NEG_INF = -(1 << 63)          # one-sided range bounds
 POS_INF = (1 << 63) - 1
 PLAN_NULL_KEY = -(1 << 63) + 1
+# gg_plan_aggkind (engine_abi.h)
+AGG_COUNT_STAR, AGG_COUNT_COL, AGG_SUM = 0, 1, 2
+AGG_MIN, AGG_MAX, AGG_AVG = 3, 4, 5
 
 
 class KernelStat(ctypes.Structure):
@@ -274,6 +277,7 @@ class Engine:
         _check(lib().gg_engine_init(ctypes.byref(cfg)), "engine_init")
         self.n_segments = n_segments
         self.segment_id = segment_id
+        self._plan_kinds = {}   # plan handle -> descriptor agg kinds
 
     def shutdown(self):
         _check(lib().gg_engine_shutdown(), "engine_shutdown")
@@ -392,7 +396,9 @@ class Engine:
                  "preds": [...]}]  (hash SEMI-join filters)
         group_cols: 0-2 column names of the driving table
         aggs: ["count"] | ("count", col) |
-              ("sum", [(col, "id"|"sub100"|"add100"), ...])
+              ("sum", [(col, "id"|"sub100"|"add100"), ...]) |
+              ("min", (col, mod)) | ("max", (col, mod)) |
+              ("avg", [(col, mod), ...])
         """
         mods = {"id": 0, "sub100": 1, "add100": 2}
 
@@ -416,47 +422,80 @@ class Engine:
         for g, c in enumerate(group_cols):
             d.group_cols[g] = c.encode()
         d.naggs = len(aggs)
+        kinds = []
         for a, spec in enumerate(aggs):
             if spec == "count" or spec == ("count",):
-                d.aggs[a].kind = 0
+                d.aggs[a].kind = AGG_COUNT_STAR
                 d.aggs[a].nfactors = 0
             elif spec[0] == "count":
-                d.aggs[a].kind = 1
+                d.aggs[a].kind = AGG_COUNT_COL
                 d.aggs[a].nfactors = 1
                 d.aggs[a].col[0] = spec[1].encode()
                 d.aggs[a].mod[0] = 0
+            elif spec[0] in ("min", "max"):
+                # exactly one factor; a factor LIST is passed through
+                # so the engine's nfactors != 1 rejection is reachable
+                fs = ([spec[1]] if isinstance(spec[1][0], str)
+                      else list(spec[1]))
+                d.aggs[a].kind = AGG_MIN if spec[0] == "min" else AGG_MAX
+                d.aggs[a].nfactors = len(fs)
+                for f, (c, m) in enumerate(fs):
+                    d.aggs[a].col[f] = c.encode()
+                    d.aggs[a].mod[f] = mods[m]
             else:
-                assert spec[0] == "sum", spec
-                d.aggs[a].kind = 2
+                assert spec[0] in ("sum", "avg"), spec
+                d.aggs[a].kind = AGG_SUM if spec[0] == "sum" else AGG_AVG
                 d.aggs[a].nfactors = len(spec[1])
                 for f, (c, m) in enumerate(spec[1]):
                     d.aggs[a].col[f] = c.encode()
                     d.aggs[a].mod[f] = mods[m]
+            kinds.append(d.aggs[a].kind)
         h = I32()
         _check(lib().gg_engine_compile_plan(ctypes.byref(d),
                                             ctypes.byref(h)), "compile_plan")
+        self._plan_kinds[h.value] = kinds
         return h.value
 
     def execute_plan(self, p, max_groups=1 << 16):
-        naggs_guess = 8
+        """One (key0, key1, vals) per group; vals holds one entry per
+        descriptor aggregate: COUNT/SUM -> int, MIN/MAX -> int or None
+        (SQL NULL), AVG -> (sum, count) for avg_str."""
+        kinds = self._plan_kinds.get(p)
+        nslots_guess = 8 if kinds is None else max(
+            8, sum(2 if k == AGG_AVG else 1 for k in kinds))
         raw = self.execute_raw(
-            p, 16 + max_groups * (16 + 16 * naggs_guess))
+            p, 16 + max_groups * (16 + 16 * nslots_guess))
         ng = int.from_bytes(raw[0:8], "little", signed=True)
-        naggs = int.from_bytes(raw[8:12], "little", signed=True)
+        nslots = int.from_bytes(raw[8:12], "little", signed=True)
+        if kinds is None:
+            kinds = [AGG_SUM] * nslots
         groups = []
         off = 16
+
+        def slot():
+            nonlocal off
+            lo = int.from_bytes(raw[off:off + 8], "little")
+            hi = int.from_bytes(raw[off + 8:off + 16], "little",
+                                signed=True)
+            off += 16
+            return lo, hi
+
         for _ in range(ng):
             k0 = int.from_bytes(raw[off:off + 8], "little", signed=True)
             k1 = int.from_bytes(raw[off + 8:off + 16], "little",
                                 signed=True)
             off += 16
             vals = []
-            for _ in range(naggs):
-                lo = int.from_bytes(raw[off:off + 8], "little")
-                hi = int.from_bytes(raw[off + 8:off + 16], "little",
-                                    signed=True)
-                vals.append((hi << 64) | lo)
-                off += 16
+            for k in kinds:
+                lo, hi = slot()
+                if k in (AGG_MIN, AGG_MAX):
+                    # lo = int64 bit pattern, hi = non-NULL inputs
+                    vals.append(None if hi == 0 else
+                                lo - (1 << 64) if lo >> 63 else lo)
+                elif k == AGG_AVG:
+                    vals.append(((hi << 64) | lo, slot()[0]))
+                else:
+                    vals.append((hi << 64) | lo)
             groups.append((k0, k1, vals))
         return groups
 

@@ -429,11 +429,12 @@ gg_status gg_engine_radix_sort_u64(uint64_t *keys, uint64_t *payload_or_null,
  * strategy-number operator classes), zero or more hash SEMI-join
  * filters against filtered build tables (nodeHash.c:88 build /
  * nodeHashjoin.c:78 probe, join-qual = key equality), a hash group-by
- * over 0–2 key columns (execHHashagg.c:905), and COUNT/SUM aggregate
- * transitions whose inputs are products of up to three column factors
- * with the (100±col) scaled-decimal modifiers TPC-H money expressions
- * need (numeric.c:1735 mul_var dscale rule; ExecTargetList
- * execQual.c:6369).  Q1/Q3/Q5-shaped descriptors keep their
+ * over 0–2 key columns (execHHashagg.c:905), and COUNT/SUM/AVG
+ * aggregate transitions whose inputs are products of up to three
+ * column factors with the (100±col) scaled-decimal modifiers TPC-H
+ * money expressions need (numeric.c:1735 mul_var dscale rule;
+ * ExecTargetList execQual.c:6369), plus MIN/MAX over one such factor
+ * (int8smaller/int8larger).  Q1/Q3/Q5-shaped descriptors keep their
  * specialized kernels via gg_engine_compile_pipeline; everything else
  * — mpph6 (Q6), changed predicate columns, ad-hoc scans — compiles
  * here with ZERO query-specific kernels.  Unsupported shapes return
@@ -471,12 +472,24 @@ typedef struct gg_plan_join
 
 /* aggregate: COUNT(*) / COUNT(col) (non-NULL, nodeAgg strict rules) /
  * SUM(f0*f1*f2), factor = col, (100-col) or (100+col); SUM skips rows
- * whose factor inputs are NULL (strict transition, nodeAgg.c:413–460) */
+ * whose factor inputs are NULL (strict transition, nodeAgg.c:413–460).
+ *
+ * MIN(f0) / MAX(f0) (int8smaller / int8larger): exactly one factor, a
+ * column of any accepted type (char1 reads as 0..255) under any
+ * gg_plan_fmod; nfactors != 1 is GG_ENOTSUP.  Strict: NULL inputs are
+ * skipped, a group with no non-NULL input yields SQL NULL.
+ *
+ * AVG(f0*f1*f2): 1..3 factors like SUM.  The transition state is the
+ * exact 128-bit sum plus the count of rows whose factors are all
+ * non-NULL (numeric_avg's state); finalise with gg_engine_avg_str. */
 typedef enum gg_plan_aggkind
 {
 	GG_AGG_COUNT_STAR = 0,
 	GG_AGG_COUNT_COL = 1,
-	GG_AGG_SUM = 2
+	GG_AGG_SUM = 2,
+	GG_AGG_MIN = 3,
+	GG_AGG_MAX = 4,
+	GG_AGG_AVG = 5
 } gg_plan_aggkind;
 
 typedef enum gg_plan_fmod
@@ -516,7 +529,25 @@ typedef struct gg_plan_desc
  *   int64 n_groups; int32 naggs; int32 ngroup;
  *   then n_groups rows, sorted by (key0, key1) ascending:
  *     int64 key0, int64 key1, then naggs x (uint64 lo, int64 hi)
- *     (each aggregate as a signed 128-bit value) */
+ * naggs is the number of 16-byte result slots per row; slots follow
+ * descriptor order:
+ *   COUNT(*), COUNT(col), SUM   1 slot: a signed 128-bit value
+ *   MIN, MAX                    1 slot: lo = the value as an int64 bit
+ *                               pattern, hi = number of non-NULL
+ *                               inputs N; hi == 0 means SQL NULL and
+ *                               lo is then 0
+ *   AVG                         2 slots: slot 0 = signed 128-bit sum;
+ *                               slot 1 = (lo = N, hi = 0); N == 0
+ *                               means SQL NULL
+ * (so naggs equals the descriptor's naggs unless it holds an AVG).
+ *
+ * Accumulator budget: on the device every aggregate occupies
+ * accumulator slots, GG_PLAN_MAX_AGGS in all.  COUNT and SUM take one;
+ * MIN and MAX take a value word plus a non-NULL count; AVG takes a sum
+ * plus a count.  The helper counts of MIN/MAX/AVG aggregates over the
+ * same factor columns are shared.  A descriptor whose lowered form
+ * needs more than GG_PLAN_MAX_AGGS slots returns GG_ENOTSUP; any
+ * descriptor with 4 or fewer aggregates compiles. */
 gg_status gg_engine_compile_plan(const gg_plan_desc *desc, gg_pipeline *out);
 
 /* Attach a NULL-flag array (1 byte per row, nonzero = NULL) to a

@@ -1,26 +1,55 @@
-/* Host-only harness: reproduce the plan_rtc codegen for a Q1-shaped
- * grouped plan and dump the generated source (GG_PLAN_RTC_DUMP).
+/* Host-only harness: reproduce the plan_rtc codegen for a few plan
+ * shapes and dump the generated source (GG_PLAN_RTC_DUMP).
  * hipRTC compiles without a GPU; module load fails afterwards on a
  * CPU-only box, which is fine — the dump is what we want.  Test/dev
- * tooling only; never part of the product path. */
+ * tooling only; never part of the product path.
+ *
+ * Usage: rtc_dump_local [DUMPFILE [SHAPE]]
+ *   q1     Q1-shaped grouped plan: generic + baked fast tier (default)
+ *   q1w    same, baked 2-word tier
+ *   q6     Q6-shaped global-group plan (generic only; never baked)
+ *   q1mm   Q1-shaped with MIN/MAX/AVG lowered slots, baked fast tier
+ *   q1mmw  same, baked 2-word tier
+ *   q6mm   global-group plan with MIN/MAX/AVG lowered slots
+ * Exit status is non-zero when a variant fails to COMPILE (a module
+ * load / function lookup failure without a GPU is not a failure). */
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 
 #include "../greengage_amd/csrc/engine_internal.h"
 
 using namespace gg;
 
-int
-main(int argc, char **argv)
-{
-	setenv("GG_PLAN_RTC_DUMP", argc > 1 ? argv[1] : "/tmp/rtc_dump.cu",
-	       0);
+static char dummy[256];	/* distinct fake pointers per column so the
+				 * load-dedup behaves as with real tables */
 
-	PlanDev D{};
-	char dummy[256];	/* distinct fake pointers per column so
-				 * the load-dedup behaves as with real
-				 * tables */
+static void
+set_agg(PlanDev &D, int a, int kind, int nf, const int *cols,
+	const int *mods)
+{
+	D.aggs[a].kind = kind;
+	D.aggs[a].nf = nf;
+	for (int f = 0; f < nf; f++)
+	{
+		D.aggs[a].col[f] = dummy + cols[f];
+		D.aggs[a].width[f] = 8;
+		D.aggs[a].mod[f] = (int8_t) mods[f];
+	}
+}
+
+/* qty/price/disc/tax as four distinct pointers, shared across aggs
+ * like the real Q1 plan */
+enum { QTY = 24, PRICE = 32, DISC = 40, TAX = 48 };
+
+static void
+shape_q1(PlanDev &D, bool mm)
+{
+	static const int c_q[] = {QTY}, c_p[] = {PRICE}, c_d[] = {DISC};
+	static const int c_pd[] = {PRICE, DISC}, c_pdt[] = {PRICE, DISC, TAX};
+	static const int m_id[] = {0, 0, 0}, m_pd[] = {0, 1},
+		m_pdt[] = {0, 1, 2};
 
 	D.n = 600000000;
 	D.npreds = 1;
@@ -28,43 +57,117 @@ main(int argc, char **argv)
 	D.preds[0].width = 4;
 	D.preds[0].lo = -2000000000;
 	D.preds[0].hi = 10000;
-	D.njoins = 0;
 	D.ngroup = 2;
 	D.gcol[0] = dummy + 8;
 	D.gcol[1] = dummy + 16;
 	D.gwidth[0] = D.gwidth[1] = 1;
-	D.naggs = 6;
-	/* count, sum(qty), sum(price), sum(disc), sum(price*(100-disc)),
-	 * sum(price*(100-disc)*(100+tax)) */
-	int kinds[6] = {0, 2, 2, 2, 2, 2};
-	int nfs[6] = {0, 1, 1, 1, 2, 3};
-	int8_t mods[6][3] = {{0}, {0}, {0}, {0}, {0, 1}, {0, 1, 2}};
-
-	for (int a = 0; a < 6; a++)
+	if (!mm)
 	{
-		D.aggs[a].kind = kinds[a];
-		D.aggs[a].nf = nfs[a];
-		/* factor columns qty/price/disc/tax as four distinct
-		 * pointers, shared across aggs like the real Q1 plan */
-		const void *cols_q1[6][3] = {
-			{}, {dummy + 24}, {dummy + 32}, {dummy + 40},
-			{dummy + 32, dummy + 40},
-			{dummy + 32, dummy + 40, dummy + 48}};
-		for (int f = 0; f < nfs[a]; f++)
-		{
-			D.aggs[a].col[f] = cols_q1[a][f];
-			D.aggs[a].width[f] = 8;
-			D.aggs[a].mod[f] = mods[a][f];
-		}
+		/* count, sum(qty), sum(price), sum(disc),
+		 * sum(price*(100-disc)), sum(price*(100-disc)*(100+tax)) */
+		D.naggs = 6;
+		set_agg(D, 0, 0, 0, nullptr, nullptr);
+		set_agg(D, 1, 2, 1, c_q, m_id);
+		set_agg(D, 2, 2, 1, c_p, m_id);
+		set_agg(D, 3, 2, 1, c_d, m_id);
+		set_agg(D, 4, 2, 2, c_pd, m_pd);
+		set_agg(D, 5, 2, 3, c_pdt, m_pdt);
+		return;
 	}
+	/* count, sum(price*(100-disc)), then the lowered form of
+	 * MIN(qty), MAX(price), AVG(disc): value word + non-NULL count,
+	 * value word + count, sum + count */
+	D.naggs = 8;
+	set_agg(D, 0, 0, 0, nullptr, nullptr);
+	set_agg(D, 1, 2, 2, c_pd, m_pd);
+	set_agg(D, 2, 3, 1, c_q, m_id);
+	set_agg(D, 3, 1, 1, c_q, m_id);
+	set_agg(D, 4, 4, 1, c_p, m_id);
+	set_agg(D, 5, 1, 1, c_p, m_id);
+	set_agg(D, 6, 2, 1, c_d, m_id);
+	set_agg(D, 7, 1, 1, c_d, m_id);
+}
 
-	long long codes[6] = {16710, 20038, 20050, 33350, 36934, 33347};
+static void
+shape_q6(PlanDev &D, bool mm)
+{
+	static const int c_pd[] = {PRICE, DISC}, c_q[] = {QTY},
+		c_p[] = {PRICE};
+	static const int m_id[] = {0, 0, 0}, m_sub[] = {1};
+
+	D.n = 600000000;
+	D.npreds = 3;
+	for (int p = 0; p < 3; p++)
+	{
+		D.preds[p].col = dummy + 64 + 8 * p;
+		D.preds[p].width = p == 0 ? 4 : 8;
+		D.preds[p].lo = 0;
+		D.preds[p].hi = 10000;
+	}
+	D.ngroup = 0;
+	D.naggs = 2;
+	set_agg(D, 0, 2, 2, c_pd, m_id);
+	set_agg(D, 1, 0, 0, nullptr, nullptr);
+	if (mm)
+	{
+		D.naggs = 6;
+		set_agg(D, 2, 3, 1, c_q, m_sub);
+		set_agg(D, 3, 1, 1, c_q, m_id);
+		set_agg(D, 4, 4, 1, c_p, m_id);
+		set_agg(D, 5, 1, 1, c_p, m_id);
+		/* one nullable input so the strict flags are live */
+		D.aggs[2].nulls[0] = D.aggs[3].nulls[0] =
+			(const uint8_t *) dummy + 128;
+	}
+}
+
+/* compile errors come back as GG_ENOTSUP with this message prefix */
+static bool
+compiled(gg_status s)
+{
+	return s == GG_OK ||
+		!std::strstr(gg_engine_last_error(), "compile failed");
+}
+
+int
+main(int argc, char **argv)
+{
+	const char *shape = argc > 2 ? argv[2] : "q1";
+	bool mm = std::strstr(shape, "mm") != nullptr;
+	bool wide = shape[std::strlen(shape) - 1] == 'w';
+
+	setenv("GG_PLAN_RTC_DUMP", argc > 1 ? argv[1] : "/tmp/rtc_dump.cu",
+	       0);
+
+	PlanDev D{};
 	std::shared_ptr<void> out;
-	gg_status s1 = plan_rtc_compile(D, false, false, &out);
-	gg_status s2 = plan_rtc_compile(D, false, false, &out, codes, 6,
-					true);
+	bool ok = true;
 
-	fprintf(stderr, "generic rc=%d baked-fast rc=%d (module-load "
-		"failure is expected without a GPU)\n", s1, s2);
-	return 0;
+	if (!std::strncmp(shape, "q6", 2))
+	{
+		shape_q6(D, mm);
+		gg_status s1 = plan_rtc_compile(D, false, false, &out);
+
+		ok = compiled(s1);
+		fprintf(stderr, "%s generic rc=%d\n", shape, s1);
+	}
+	else
+	{
+		long long codes[6] = {16710, 20038, 20050, 33350, 36934,
+			33347};
+
+		shape_q1(D, mm);
+		gg_status s1 = plan_rtc_compile(D, false, false, &out);
+
+		ok = compiled(s1);
+		gg_status s2 = plan_rtc_compile(D, false, false, &out, codes,
+						6, !wide);
+
+		ok = ok && compiled(s2);
+		fprintf(stderr, "%s generic rc=%d baked-%s rc=%d\n", shape,
+			s1, wide ? "2word" : "fast", s2);
+	}
+	fprintf(stderr, "last error: %s\n(a module-load failure is expected "
+		"without a GPU)\n", gg_engine_last_error());
+	return ok ? 0 : 1;
 }
