@@ -634,6 +634,9 @@ struct PlanBuildDev
 	uint64_t hslots;
 };
 
+/* blocks of 256 threads for n rows, clamped to [1, 2048]: the grid of
+ * every plan kernel, interpreted or generated */
+int pl_grid(int64_t n);
 hipError_t launch_plan_build(hipStream_t s, const PlanBuildDev &b);
 hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p);
 hipError_t launch_plan_compact(hipStream_t s,

@@ -299,6 +299,125 @@ static uint64_t next_pow2_pl(uint64_t v)
 static constexpr uint64_t PL_NSLOTS = 1ull << 18;
 static constexpr unsigned long long PL_EMPTY_HOST = 0x8000000000000000ull;
 
+/* empty the group table, zero the accumulators and the error word */
+static gg_status
+plan_reset_table(hipStream_t s, const PlanDev &D)
+{
+	GG_HIP(launch_fill_u64(s, D.tkeys, D.nslots, PL_EMPTY_HOST));
+	GG_HIP(hipMemsetAsync(D.tvals, 0, D.nslots * (size_t) D.naggs * 16,
+			      s));
+	GG_HIP(hipMemsetAsync(D.err, 0, 8, s));
+	return GG_OK;
+}
+
+/* scan with the generated kernel k (nullptr = the interpreted kernel),
+ * compact the used slots into dout / ctr, wait, and read the kernels'
+ * error word.  A running timer tm is stopped right after the scan's
+ * launch and booked on the plan_scan_agg stat row. */
+static gg_status
+plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
+		  const std::shared_ptr<void> &k, Timed *tm,
+		  unsigned long long *dout, unsigned long long *ctr,
+		  unsigned long long *herr)
+{
+	const PlanDev &D = R->dev;
+
+	if (k)
+		GG_TRY(plan_rtc_launch(e.stream, k, D, pl_grid(D.n), 256));
+	else
+		GG_HIP(launch_plan_scan_agg(e.stream, D));
+	if (tm)
+	{
+		double ms = tm->stop();
+		KernelStatAcc &st = p->stat("plan_scan_agg");
+
+		st.launches++;
+		st.total_ms += ms;
+		st.rows_in += R->scan_rows;
+		st.hbm_bytes += R->scan_rows * R->pred_bytes_per_row;
+	}
+	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
+	GG_HIP(launch_plan_compact(e.stream, D.tkeys, D.tvals, D.nslots,
+				   D.naggs, dout, ctr, D.nslots));
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_HIP(hipMemcpy(herr, D.err, 8, hipMemcpyDeviceToHost));
+	return GG_OK;
+}
+
+/* overflow-budget proof for the fire-and-forget
+ * LDS tier: interval-bound every aggregate value
+ * from cached column min/max (immutable data).
+ * All values must be non-negative and
+ * bound * rows_per_block must clear 2^61 with a
+ * 4x margin (long double keeps int64 exact; the
+ * margin absorbs product rounding). */
+static bool
+plan_fast_tier_provable(Engine &e, const PlanDev &D)
+{
+	long double rows_pb = (long double) D.n /
+		(long double) pl_grid(D.n) + 256.0L;
+
+	for (int a = 0; a < D.naggs; a++)
+	{
+		const PlanAggDev &A = D.aggs[a];
+		long double lo = 1.0L, hi = 1.0L;
+
+		/* counts add [1,1]; MIN/MAX words
+		 * combine by max over a full u64
+		 * word and take no part in the
+		 * additive bound; an AVG's sum is
+		 * a kind-2 slot like any SUM */
+		if (A.kind != 2)
+			continue;
+		for (int f = 0; f < A.nf; f++)
+		{
+			long long mn, mx;
+
+			if (engine_col_minmax(e, A.col[f], A.width[f], D.n,
+					      &mn, &mx) != GG_OK)
+				return false;
+			long double a0 = (long double) mn;
+			long double a1 = (long double) mx;
+
+			if (A.mod[f] == 1)
+			{
+				long double t0 = 100.0L - a1;
+				long double t1 = 100.0L - a0;
+
+				a0 = t0;
+				a1 = t1;
+			}
+			else if (A.mod[f] == 2)
+			{
+				a0 = 100.0L + a0;
+				a1 = 100.0L + a1;
+			}
+			{
+				long double c[4] = {
+					lo * a0, lo * a1,
+					hi * a0, hi * a1};
+				long double nl = c[0],
+					nh = c[0];
+
+				for (int q = 1; q < 4; q++)
+				{
+					if (c[q] < nl)
+						nl = c[q];
+					if (c[q] > nh)
+						nh = c[q];
+				}
+				lo = nl;
+				hi = nh;
+			}
+		}
+		if (lo < 0.0L ||
+		    hi * rows_pb >=
+		    2305843009213693952.0L) /* 2^61 */
+			return false;
+	}
+	return true;
+}
+
 gg_status
 exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 {
@@ -379,32 +498,34 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			: "path_plan_join_hash").launches++;
 	}
 
-	/* 2. group table + fused scan */
+	/* 2. group table + fused scan, 3. compact */
 	uint64_t nslots = R->dev.ngroup == 0 ? 1
 		: (R->dev.ngroup == 2 ? 1 << 19 : PL_NSLOTS);
 	int naggs = R->dev.naggs;
+	uint64_t cap = nslots;
+	int rowsz = 1 + 2 * naggs;
 	unsigned long long *tkeys = (unsigned long long *)
 		p->sget("plan.tkeys", nslots * 8);
 	unsigned long long *tvals = (unsigned long long *)
 		p->sget("plan.tvals", nslots * (size_t) naggs * 16);
 	unsigned long long *derr = (unsigned long long *)
 		p->sget("plan.err", 8);
+	unsigned long long *dout = (unsigned long long *)
+		p->sget("plan.out", cap * (size_t) rowsz * 8);
+	unsigned long long ng = 0, herr = 0;
 
 	if (!tkeys || !tvals || !derr)
 		return fail(GG_ENOMEM, "plan group table");
+	if (!dout)
+		return fail(GG_ENOMEM, "plan out");
+	R->dev.tkeys = tkeys;
+	R->dev.tvals = tvals;
+	R->dev.nslots = nslots;
+	R->dev.err = derr;
 	{
 		Timed tm(e.stream);
 
-		GG_HIP(launch_fill_u64(e.stream, tkeys, nslots,
-				       PL_EMPTY_HOST));
-		GG_HIP(hipMemsetAsync(tvals, 0,
-				      nslots * (size_t) naggs * 16,
-				      e.stream));
-		GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
-		R->dev.tkeys = tkeys;
-		R->dev.tvals = tvals;
-		R->dev.nslots = nslots;
-		R->dev.err = derr;
+		GG_TRY(plan_reset_table(e.stream, R->dev));
 		if (!R->rtc_tried)
 		{
 			/* specialize now: bitmap-vs-hash join shape is
@@ -417,47 +538,10 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			p->stat(rs == GG_OK ? "path_plan_rtc"
 				: "path_plan_interp").launches++;
 		}
-		if (R->rtc)
-		{
-			int64_t g = (R->dev.n + 255) / 256;
-
-			if (g > 2048)
-				g = 2048;
-			if (g < 1)
-				g = 1;
-			GG_TRY(plan_rtc_launch(
-				e.stream,
-				R->rtc_baked ? R->rtc_baked : R->rtc,
-				R->dev, (int) g, 256));
-		}
-		else
-			GG_HIP(launch_plan_scan_agg(e.stream, R->dev));
-		{
-			double ms = tm.stop();
-			KernelStatAcc &st = p->stat("plan_scan_agg");
-
-			st.launches++;
-			st.total_ms += ms;
-			st.rows_in += R->scan_rows;
-			st.hbm_bytes += R->scan_rows *
-				R->pred_bytes_per_row;
-		}
+		GG_TRY(plan_scan_compact(e, p, R,
+					 R->rtc_baked ? R->rtc_baked : R->rtc,
+					 &tm, dout, ctr, &herr));
 	}
-
-	/* 3. compact + host sort */
-	uint64_t cap = nslots;
-	int rowsz = 1 + 2 * naggs;
-	unsigned long long *dout = (unsigned long long *)
-		p->sget("plan.out", cap * (size_t) rowsz * 8);
-	unsigned long long ng = 0, herr = 0;
-
-	if (!dout)
-		return fail(GG_ENOMEM, "plan out");
-	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-	GG_HIP(launch_plan_compact(e.stream, tkeys, tvals, nslots, naggs,
-				   dout, ctr, cap));
-	GG_HIP(hipStreamSynchronize(e.stream));
-	GG_HIP(hipMemcpy(&herr, derr, 8, hipMemcpyDeviceToHost));
 	if (herr == 2ull && R->rtc_baked)
 	{
 		/* the baked kernel saw a group code outside its baked
@@ -466,27 +550,9 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		 * generic kernel */
 		R->rtc_baked.reset();
 		p->stat("path_plan_bake_miss").launches++;
-		GG_HIP(launch_fill_u64(e.stream, tkeys, nslots,
-				       PL_EMPTY_HOST));
-		GG_HIP(hipMemsetAsync(tvals, 0,
-				      nslots * (size_t) naggs * 16,
-				      e.stream));
-		GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
-		{
-			int64_t g = (R->dev.n + 255) / 256;
-
-			if (g > 2048)
-				g = 2048;
-			if (g < 1)
-				g = 1;
-			GG_TRY(plan_rtc_launch(e.stream, R->rtc, R->dev,
-					       (int) g, 256));
-		}
-		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-		GG_HIP(launch_plan_compact(e.stream, tkeys, tvals, nslots,
-					   naggs, dout, ctr, cap));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_HIP(hipMemcpy(&herr, derr, 8, hipMemcpyDeviceToHost));
+		GG_TRY(plan_reset_table(e.stream, R->dev));
+		GG_TRY(plan_scan_compact(e, p, R, R->rtc, nullptr, dout, ctr,
+					 &herr));
 	}
 	if (herr)
 		return fail(GG_EINVAL,
@@ -706,91 +772,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			for (size_t i = 0; i < ng; i++)
 				codes[i] = (long long) rows[i * rowsz];
 
-			/* overflow-budget proof for the fire-and-forget
-			 * LDS tier: interval-bound every aggregate value
-			 * from cached column min/max (immutable data).
-			 * All values must be non-negative and
-			 * bound * rows_per_block must clear 2^61 with a
-			 * 4x margin (long double keeps int64 exact; the
-			 * margin absorbs product rounding). */
-			bool fastok = true;
-			int64_t grid = (R->dev.n + 255) / 256;
-
-			if (grid > 2048)
-				grid = 2048;
-			if (grid < 1)
-				grid = 1;
-			{
-				long double rows_pb = (long double)
-					R->dev.n / (long double) grid + 256.0L;
-
-				for (int a = 0;
-				     fastok && a < R->dev.naggs; a++)
-				{
-					const PlanAggDev &A = R->dev.aggs[a];
-					long double lo = 1.0L, hi = 1.0L;
-
-					/* counts add [1,1]; MIN/MAX words
-					 * combine by max over a full u64
-					 * word and take no part in the
-					 * additive bound; an AVG's sum is
-					 * a kind-2 slot like any SUM */
-					if (A.kind != 2)
-						continue;
-					for (int f = 0;
-					     fastok && f < A.nf; f++)
-					{
-						long long mn, mx;
-
-						if (engine_col_minmax(
-							e, A.col[f],
-							A.width[f],
-							R->dev.n, &mn,
-							&mx) != GG_OK)
-						{
-							fastok = false;
-							break;
-						}
-						long double a0 = (long double) mn;
-						long double a1 = (long double) mx;
-
-						if (A.mod[f] == 1)
-						{
-							long double t0 = 100.0L - a1;
-							long double t1 = 100.0L - a0;
-
-							a0 = t0;
-							a1 = t1;
-						}
-						else if (A.mod[f] == 2)
-						{
-							a0 = 100.0L + a0;
-							a1 = 100.0L + a1;
-						}
-						{
-							long double c[4] = {
-								lo * a0, lo * a1,
-								hi * a0, hi * a1};
-							long double nl = c[0],
-								nh = c[0];
-
-							for (int q = 1; q < 4; q++)
-							{
-								if (c[q] < nl)
-									nl = c[q];
-								if (c[q] > nh)
-									nh = c[q];
-							}
-							lo = nl;
-							hi = nh;
-						}
-					}
-					if (lo < 0.0L ||
-					    hi * rows_pb >=
-					    2305843009213693952.0L) /* 2^61 */
-						fastok = false;
-				}
-			}
+			bool fastok = plan_fast_tier_provable(e, R->dev);
 			gg_status rs = plan_rtc_compile(
 				R->dev, R->dev.gnulls[0] != nullptr,
 				R->dev.gnulls[1] != nullptr, &R->rtc_baked,

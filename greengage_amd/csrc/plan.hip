@@ -36,7 +36,9 @@ namespace gg
 static constexpr int PL_THREADS = 256;
 static constexpr int PL_MAX_BLOCKS = 2048;
 
-static inline int pl_grid(int64_t n)
+/* the one grid clamp of the plan kernels, interpreted and generated
+ * (plan.cpp sizes the hipRTC launches and the fast-tier proof by it) */
+int pl_grid(int64_t n)
 {
 	int64_t b = (n + PL_THREADS - 1) / PL_THREADS;
 
@@ -300,30 +302,9 @@ pl_agg_val(const PlanAggDev &a, int64_t i, __int128 *out)
 	}
 }
 
-/* register-accumulator transition: exact 128-bit add, or unsigned max
- * of the encoded MIN/MAX word */
-template <int MM>
-__device__ static inline void
-pl_reg_acc(int kind, unsigned long long &lo, long long &hi, __int128 v)
-{
-	unsigned long long vlo = (unsigned long long) v;
-
-	if (MM && kind >= 3)
-	{
-		if (vlo > lo)
-			lo = vlo;
-		return;
-	}
-	{
-		unsigned long long old = lo;
-
-		lo += vlo;
-		hi += (long long) (v >> 64) + (lo < old);
-	}
-}
-
 static constexpr unsigned long long PL_EMPTY = 0x8000000000000000ull;
 
+/* group-table find-or-create (execHHashagg.c:905); -1 = table full */
 __device__ static inline int64_t
 pl_slot(const PlanDev &P, long long code)
 {
@@ -351,17 +332,84 @@ pl_slot(const PlanDev &P, long long code)
 	return -1;
 }
 
+/* exact two-word add into registers */
 __device__ static inline void
-pl_atomic_add128(unsigned long long *lo, unsigned long long *hi, __int128 v)
+pl_add128(unsigned long long &lo, unsigned long long &hi,
+	  unsigned long long vlo, unsigned long long vhi)
 {
-	unsigned long long vlo = (unsigned long long) v;
-	unsigned long long vhi = (unsigned long long) (v >> 64);
-	unsigned long long old = atomicAdd(lo, vlo);
+	unsigned long long old = lo;
+
+	lo += vlo;
+	hi += vhi + (lo < old);
+}
+
+/* ... and into an accumulator w[0..1] in LDS or global memory; the
+ * carry comes from the returned old low word */
+__device__ static inline void
+pl_atomic_add128(unsigned long long *w, unsigned long long vlo,
+		 unsigned long long vhi)
+{
+	unsigned long long old = atomicAdd(w, vlo);
 
 	if (old + vlo < old)
 		vhi++;
 	if (vhi)
-		atomicAdd(hi, vhi);
+		atomicAdd(w + 1, vhi);
+}
+
+/* one row's transitions: every aggregate's value into its two-word
+ * accumulator acc(a).  ATOMIC = the accumulators live in LDS
+ * or global memory, else in registers.  Exact 128-bit add, or unsigned
+ * max of the encoded MIN/MAX word. */
+template <int MM, bool ATOMIC, class Acc>
+__device__ static inline void
+pl_row_aggs(const PlanDev &P, int64_t i, Acc acc)
+{
+	for (int a = 0; a < P.naggs; a++)
+	{
+		__int128 v;
+
+		if (!pl_agg_val<MM>(P.aggs[a], i, &v))
+			continue;
+		unsigned long long vlo = (unsigned long long) v;
+		unsigned long long vhi = (unsigned long long) (v >> 64);
+		unsigned long long *w = acc(a);
+
+		if (MM && P.aggs[a].kind >= 3)
+		{
+			if (ATOMIC)
+				atomicMax(w, vlo);
+			else if (vlo > w[0])
+				w[0] = vlo;
+		}
+		else if (ATOMIC)
+			pl_atomic_add128(w, vlo, vhi);
+		else
+			pl_add128(w[0], w[1], vlo, vhi);
+	}
+}
+
+/* fold the replicas of accumulator a (replica rr's words at rep(rr))
+ * and flush the result into the global accumulator dst */
+template <int MM, int NREP, class Rep>
+__device__ static inline void
+pl_fold_flush(int kind, unsigned long long *dst, Rep rep)
+{
+	unsigned long long lo = 0, hi = 0;
+
+	if (MM && kind >= 3)
+	{
+		for (int rr = 0; rr < NREP; rr++)
+			if (rep(rr)[0] > lo)
+				lo = rep(rr)[0];
+		if (lo)
+			atomicMax(dst, lo);
+		return;
+	}
+	for (int rr = 0; rr < NREP; rr++)
+		pl_add128(lo, hi, rep(rr)[0], rep(rr)[1]);
+	if (lo || hi)
+		pl_atomic_add128(dst, lo, hi);
 }
 
 template <int NT, int MM>
@@ -370,30 +418,24 @@ void k_plan_scan_agg(PlanDev P)
 {
 	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
 
+	/* Both group modes scan the same way: 4-way strided rows with
+	 * unconditional predicate streams, then the tail.  The loop is
+	 * spelled out per mode on purpose: shared through a lambda or a
+	 * template it is optimized before the row body is inlined and the
+	 * whole kernel compiles differently (4789 instead of 5960
+	 * instructions), which this kernel's measured speed never saw. */
 	if (P.ngroup == 0)
 	{
 		/* global-group fast path: register accumulators, one
 		 * wave-reduced atomic flush per wave (the Q1/sumprice
-		 * pattern — keeps e.g. Q6 at streaming rate); 4-way
-		 * strided rows with unconditional predicate streams */
-		unsigned long long alo[GG_PLAN_MAX_AGGS] = {};
-		long long ahi[GG_PLAN_MAX_AGGS] = {};
-
-		auto tail = [&](int64_t i)
+		 * pattern — keeps e.g. Q6 at streaming rate) */
+		unsigned long long acc[GG_PLAN_MAX_AGGS][2] = {};
+		auto row = [&](int64_t i)
 		{
-			if (!pl_preds_pass<NT>(P.preds, P.npreds, i))
-				return;
 			if (!pl_joins_pass(P.joins, P.njoins, i))
 				return;
-			for (int a = 0; a < P.naggs; a++)
-			{
-				__int128 v;
-
-				if (!pl_agg_val<MM>(P.aggs[a], i, &v))
-					continue;
-				pl_reg_acc<MM>(P.aggs[a].kind, alo[a], ahi[a],
-					       v);
-			}
+			pl_row_aggs<MM, false>(P, i,
+					       [&](int a) { return acc[a]; });
 		};
 		int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 
@@ -403,26 +445,12 @@ void k_plan_scan_agg(PlanDev P)
 
 			pl_preds_pass4<NT>(P.preds, P.npreds, i, stride, ok);
 			for (int j = 0; j < 4; j++)
-			{
-				int64_t r = i + j * stride;
-
-				if (!ok[j])
-					continue;
-				if (!pl_joins_pass(P.joins, P.njoins, r))
-					continue;
-				for (int a = 0; a < P.naggs; a++)
-				{
-					__int128 v;
-
-					if (!pl_agg_val<MM>(P.aggs[a], r, &v))
-						continue;
-					pl_reg_acc<MM>(P.aggs[a].kind, alo[a],
-						       ahi[a], v);
-				}
-			}
+				if (ok[j])
+					row(i + j * stride);
 		}
 		for (; i < P.n; i += stride)
-			tail(i);
+			if (pl_preds_pass<NT>(P.preds, P.npreds, i))
+				row(i);
 		for (int a = 0; a < P.naggs; a++)
 		{
 			if (MM && P.aggs[a].kind >= 3)
@@ -432,31 +460,22 @@ void k_plan_scan_agg(PlanDev P)
 				for (int off = 32; off; off >>= 1)
 				{
 					unsigned long long o =
-						__shfl_down(alo[a], off, 64);
+						__shfl_down(acc[a][0], off, 64);
 
-					if (o > alo[a])
-						alo[a] = o;
+					if (o > acc[a][0])
+						acc[a][0] = o;
 				}
-				if ((threadIdx.x & 63) == 0 && alo[a])
-					atomicMax(&P.tvals[2 * a], alo[a]);
+				if ((threadIdx.x & 63) == 0 && acc[a][0])
+					atomicMax(&P.tvals[2 * a], acc[a][0]);
 				continue;
 			}
 			for (int off = 32; off; off >>= 1)
-			{
-				unsigned long long olo = alo[a];
-
-				alo[a] += __shfl_down(alo[a], off, 64);
-				ahi[a] += __shfl_down(ahi[a], off, 64) +
-					(long long) (alo[a] < olo);
-			}
-			if ((threadIdx.x & 63) == 0 && (alo[a] || ahi[a]))
-			{
-				__int128 v = ((__int128) ahi[a] << 64) |
-					(__int128) alo[a];
-
-				pl_atomic_add128(&P.tvals[2 * a],
-						 &P.tvals[2 * a + 1], v);
-			}
+				pl_add128(acc[a][0], acc[a][1],
+					  __shfl_down(acc[a][0], off, 64),
+					  __shfl_down(acc[a][1], off, 64));
+			if ((threadIdx.x & 63) == 0 && (acc[a][0] || acc[a][1]))
+				pl_atomic_add128(&P.tvals[2 * a], acc[a][0],
+						 acc[a][1]);
 		}
 		/* mark slot 0 used so compaction emits the group */
 		if (blockIdx.x == 0 && threadIdx.x == 0)
@@ -489,8 +508,48 @@ void k_plan_scan_agg(PlanDev P)
 
 	const int lrep = (int) (threadIdx.x & (LREPL - 1));
 
-	auto global_row = [&](int64_t i, long long code)
+	auto row = [&](int64_t i)
 	{
+		if (!pl_joins_pass(P.joins, P.njoins, i))
+			return;
+		long long code = pl_group_code(P, i);
+		int ls = -1;
+		uint32_t pos = (uint32_t) gg_hashint8(code) & (LSLOTS - 1);
+
+		for (int probe = 0; probe < 8; probe++)
+		{
+			long long cur = lkeys[pos];
+
+			if (cur == code)
+			{
+				ls = (int) pos;
+				break;
+			}
+			if (cur == LEMPTY)
+			{
+				long long prev = atomicCAS(
+					(unsigned long long *) &lkeys[pos],
+					(unsigned long long) LEMPTY,
+					(unsigned long long) code);
+
+				if (prev == LEMPTY || prev == code)
+				{
+					ls = (int) pos;
+					break;
+				}
+				continue;
+			}
+			pos = (pos + 1) & (LSLOTS - 1);
+		}
+		if (ls >= 0)
+		{
+			pl_row_aggs<MM, true>(P, i, [&](int a)
+			{
+				return &lvals[lrep][ls][2 * a];
+			});
+			return;
+		}
+		/* cache full: straight into the global table */
 		int64_t slot = pl_slot(P, code);
 
 		if (slot < 0)
@@ -498,89 +557,10 @@ void k_plan_scan_agg(PlanDev P)
 			atomicOr(P.err, 1ull);
 			return;
 		}
-		for (int a = 0; a < P.naggs; a++)
+		pl_row_aggs<MM, true>(P, i, [&](int a)
 		{
-			__int128 v;
-
-			if (!pl_agg_val<MM>(P.aggs[a], i, &v))
-				continue;
-			if (MM && P.aggs[a].kind >= 3)
-				atomicMax(&P.tvals[(slot * P.naggs + a) * 2],
-					  (unsigned long long) v);
-			else
-				pl_atomic_add128(
-					&P.tvals[(slot * P.naggs + a) * 2],
-					&P.tvals[(slot * P.naggs + a) * 2 + 1],
-					v);
-		}
-	};
-	auto grouped_row = [&](int64_t i)
-	{
-		if (!pl_joins_pass(P.joins, P.njoins, i))
-			return;
-		{
-			long long code = pl_group_code(P, i);
-			int ls = -1;
-			uint32_t pos = (uint32_t) gg_hashint8(code) &
-				(LSLOTS - 1);
-
-			for (int probe = 0; probe < 8; probe++)
-			{
-				long long cur = lkeys[pos];
-
-				if (cur == code)
-				{
-					ls = (int) pos;
-					break;
-				}
-				if (cur == LEMPTY)
-				{
-					long long prev = atomicCAS(
-						(unsigned long long *)
-						&lkeys[pos],
-						(unsigned long long) LEMPTY,
-						(unsigned long long) code);
-
-					if (prev == LEMPTY || prev == code)
-					{
-						ls = (int) pos;
-						break;
-					}
-					continue;
-				}
-				pos = (pos + 1) & (LSLOTS - 1);
-			}
-			if (ls < 0)
-			{
-				global_row(i, code);	/* cache full */
-				return;
-			}
-			for (int a = 0; a < P.naggs; a++)
-			{
-				__int128 v;
-
-				if (!pl_agg_val<MM>(P.aggs[a], i, &v))
-					continue;
-				if (MM && P.aggs[a].kind >= 3)
-					atomicMax(&lvals[lrep][ls][2 * a],
-						  (unsigned long long) v);
-				else
-				{
-					unsigned long long vlo =
-						(unsigned long long) v;
-					unsigned long long vhi =
-						(unsigned long long) (v >> 64);
-					unsigned long long old = atomicAdd(
-						&lvals[lrep][ls][2 * a], vlo);
-
-					if (old + vlo < old)
-						vhi++;
-					if (vhi)
-						atomicAdd(&lvals[lrep][ls]
-							  [2 * a + 1], vhi);
-				}
-			}
-		}
+			return &P.tvals[(slot * P.naggs + a) * 2];
+		});
 	};
 	int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 
@@ -591,11 +571,11 @@ void k_plan_scan_agg(PlanDev P)
 		pl_preds_pass4<NT>(P.preds, P.npreds, i, stride, ok);
 		for (int j = 0; j < 4; j++)
 			if (ok[j])
-				grouped_row(i + j * stride);
+				row(i + j * stride);
 	}
 	for (; i < P.n; i += stride)
 		if (pl_preds_pass<NT>(P.preds, P.npreds, i))
-			grouped_row(i);
+			row(i);
 
 	/* flush the block's LDS groups into the global table */
 	__syncthreads();
@@ -603,58 +583,18 @@ void k_plan_scan_agg(PlanDev P)
 	{
 		if (lkeys[s] == LEMPTY)
 			continue;
+		int64_t slot = pl_slot(P, lkeys[s]);
+
+		if (slot < 0)
 		{
-			int64_t slot = pl_slot(P, lkeys[s]);
-
-			if (slot < 0)
-			{
-				atomicOr(P.err, 1ull);
-				continue;
-			}
-			for (int a = 0; a < P.naggs; a++)
-			{
-				unsigned long long lo = 0, hi = 0;
-
-				if (MM && P.aggs[a].kind >= 3)
-				{
-					for (int rr = 0; rr < LREPL; rr++)
-						if (lvals[rr][s][2 * a] > lo)
-							lo = lvals[rr][s][2 * a];
-					if (lo)
-						atomicMax(
-							&P.tvals[(slot *
-								  P.naggs + a)
-								 * 2], lo);
-					continue;
-				}
-				for (int rr = 0; rr < LREPL; rr++)
-				{
-					unsigned long long rl =
-						lvals[rr][s][2 * a];
-					unsigned long long o = lo;
-
-					lo += rl;
-					hi += lvals[rr][s][2 * a + 1] +
-						(lo < o);
-				}
-
-				if (!lo && !hi)
-					continue;
-				{
-					unsigned long long old = atomicAdd(
-						&P.tvals[(slot * P.naggs + a)
-							 * 2], lo);
-
-					if (old + lo < old)
-						hi++;
-					if (hi)
-						atomicAdd(
-							&P.tvals[(slot *
-								  P.naggs + a)
-								 * 2 + 1], hi);
-				}
-			}
+			atomicOr(P.err, 1ull);
+			continue;
 		}
+		for (int a = 0; a < P.naggs; a++)
+			pl_fold_flush<MM, LREPL>(
+				P.aggs[a].kind,
+				&P.tvals[(slot * P.naggs + a) * 2],
+				[&](int rr) { return &lvals[rr][s][2 * a]; });
 	}
 }
 

@@ -17,6 +17,8 @@
  * kernel (stat row path_plan_interp); GG_PLAN_RTC=0 disables JIT.
  */
 #include <hip/hiprtc.h>
+#include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -145,34 +147,172 @@ static void emit_ld(std::string &s, const char *dst, const char *ptr,
 	s += buf;
 }
 
-/* generate + compile; returns GG_OK with *out set, or non-OK (caller
- * falls back to the interpreted kernel) */
-gg_status
-plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
-		 std::shared_ptr<void> *out, const long long *bake,
-		 int nbake, bool fast)
+static std::string fmt(const char *f, ...)
+	__attribute__((format(printf, 1, 2)));
+static std::string fmt(const char *f, ...)
 {
-	const char *dis = getenv("GG_PLAN_RTC");
+	char buf[1024];
+	va_list ap;
 
-	if (dis && dis[0] == '0')
-		return fail(GG_ENOTSUP, "rtc disabled");
-	if (nbake <= 0)
-		fast = false;	/* the u64 fast tier exists only baked */
+	va_start(ap, f);
+	std::vsnprintf(buf, sizeof(buf), f, ap);
+	va_end(ap);
+	return buf;
+}
 
-	/* NT loads: measured FLAT while the row loop carried the dead
-	 * fallback (4.90 vs 4.96 ms, r02k) but +12% once the loop got
-	 * lean (4.20 -> 3.76 ms, r02nt2) — same physics as k_q1_agg's
-	 * +11%.  Default ON for baked kernels; GG_PLAN_RTC_NT=0 reverts. */
-	const char *ntv = getenv("GG_PLAN_RTC_NT");
-	bool nt = nbake > 0 && !(ntv && ntv[0] == '0');
+/* device helpers every generated kernel shares; the host emitters below
+ * emit CALLS to these, one per accumulator, never their bodies.  All
+ * are inlined, so an LDS destination still gets ds_* atomics. */
+static const char *DEVICE_FNS = R"GG(
+#define LSLOTS 32
+#define LEMPTY ((long long) 0x8000000000000000ull)
 
-	std::string s = STRUCT_DEFS;
-	char buf[512];
+/* group-table find-or-create (execHHashagg.c:905); -1 = table full */
+__device__ inline int64_t gg_slot(const PlanDev &P, long long code)
+{
+	uint64_t pos = (uint64_t) gg_hashint8(code) & (P.nslots - 1);
+
+	for (uint64_t it = 0; it < P.nslots; it++)
+	{
+		unsigned long long cur = P.tkeys[pos];
+
+		if (cur == (unsigned long long) code)
+			return (int64_t) pos;
+		if (cur == 0x8000000000000000ull)
+		{
+			unsigned long long prev = atomicCAS(
+				&P.tkeys[pos], 0x8000000000000000ull,
+				(unsigned long long) code);
+
+			if (prev == 0x8000000000000000ull ||
+			    prev == (unsigned long long) code)
+				return (int64_t) pos;
+			continue;
+		}
+		pos = (pos + 1) & (P.nslots - 1);
+	}
+	return -1;
+}
+
+/* register accumulators: exact two-word add, and the unsigned max that
+ * combines order-encoded MIN/MAX words (0 = identity = "no input") */
+__device__ inline void gg_add2(unsigned long long &lo, unsigned long long &hi,
+			       unsigned long long vlo, unsigned long long vhi)
+{
+	unsigned long long old = lo;
+
+	lo += vlo;
+	hi += vhi + (lo < old);
+}
+
+__device__ inline void gg_max(unsigned long long &m, unsigned long long v)
+{
+	if (v > m)
+		m = v;
+}
+
+/* two-word add into an accumulator w[0..1] in LDS or global memory; the
+ * carry comes from the RETURNED old low word */
+__device__ inline void gg_atomic_add2(unsigned long long *w,
+				      unsigned long long vlo,
+				      unsigned long long vhi)
+{
+	unsigned long long old = atomicAdd(w, vlo);
+
+	if (old + vlo < old)
+		vhi++;
+	if (vhi)
+		atomicAdd(w + 1, vhi);
+}
+
+/* global-group epilogue: wave-reduce a register accumulator, one global
+ * atomic per wave */
+__device__ inline void gg_wave_flush_add(unsigned long long *dst,
+					 unsigned long long lo,
+					 unsigned long long hi)
+{
+	for (int off = 32; off; off >>= 1)
+		gg_add2(lo, hi, __shfl_down(lo, off, 64),
+			__shfl_down(hi, off, 64));
+	if ((threadIdx.x & 63) == 0 && (lo || hi))
+		gg_atomic_add2(dst, lo, hi);
+}
+
+__device__ inline void gg_wave_flush_max(unsigned long long *dst,
+					 unsigned long long m)
+{
+	for (int off = 32; off; off >>= 1)
+		gg_max(m, __shfl_down(m, off, 64));
+	if ((threadIdx.x & 63) == 0 && m)
+		atomicMax(dst, m);
+}
+
+/* grouped epilogue: fold the LREPL LDS replicas of one accumulator and
+ * flush into the global table.  w0 is the accumulator's first word in
+ * replica `rr`; the one-word tier is overflow-proven, so its fold needs
+ * no carry.  Macros, not functions: as a function the replica loop is
+ * unrolled on its own before it is inlined and the flush epilogue then
+ * compiles to different code (Q1 baked: 38 instructions and 4 VGPRs
+ * less, row loop unchanged); as a macro the program stays
+ * instruction-identical to the hand-expanded form it replaces. */
+#define GG_FOLD_FLUSH_ADD(dst, w0) \
+	do { \
+		unsigned long long lo = 0, hi = 0; \
+		for (int rr = 0; rr < LREPL; rr++) \
+			if (LW == 1) \
+				lo += (w0); \
+			else \
+				gg_add2(lo, hi, (w0), (&(w0))[1]); \
+		if (lo || hi) \
+			gg_atomic_add2((dst), lo, hi); \
+	} while (0)
+
+#define GG_FOLD_FLUSH_MAX(dst, w0) \
+	do { \
+		unsigned long long m = 0; \
+		for (int rr = 0; rr < LREPL; rr++) \
+			gg_max(m, (w0)); \
+		if (m) \
+			atomicMax((dst), m); \
+	} while (0)
+)GG";
+
+/* everything one generated program is specialized on */
+struct Gen
+{
+	const PlanDev &D;
+	bool gnull[2];
+	const long long *bake;
+	int nbake;
+	bool fast;		/* baked one-word tier */
+	bool nt;		/* nontemporal scan loads */
+};
+
+/* layout guards, tunables and the device helpers */
+static void emit_prelude(std::string &s, const Gen &G)
+{
+	const PlanDev &D = G.D;
+
+	s += STRUCT_DEFS;
+	/* the struct text above is a hand copy of engine_internal.h: pin
+	 * every size and the offsets the kernels rely on */
+	s += fmt("static_assert(sizeof(PlanPredDev) == %zu, \"layout\");\n"
+		 "static_assert(sizeof(PlanJoinDev) == %zu, \"layout\");\n"
+		 "static_assert(sizeof(PlanAggDev) == %zu, \"layout\");\n"
+		 "static_assert(sizeof(PlanDev) == %zu, \"layout\");\n",
+		 sizeof(PlanPredDev), sizeof(PlanJoinDev), sizeof(PlanAggDev),
+		 sizeof(PlanDev));
+	s += fmt("static_assert(__builtin_offsetof(PlanDev, joins) == %zu, \"layout\");\n"
+		 "static_assert(__builtin_offsetof(PlanDev, tkeys) == %zu, \"layout\");\n"
+		 "static_assert(__builtin_offsetof(PlanDev, err) == %zu, \"layout\");\n"
+		 "static_assert(__builtin_offsetof(PlanDev, aggs) == %zu, \"layout\");\n",
+		 offsetof(PlanDev, joins), offsetof(PlanDev, tkeys),
+		 offsetof(PlanDev, err), offsetof(PlanDev, aggs));
 
 	/* baked variant: more replicas by default — the accumulator
 	 * array has only nbake slots, so per-word contention is higher
 	 * and LDS is cheap (k_q1_agg makes the same trade) */
-	int lrepl = nbake > 0 ? 16 : 8;
+	int lrepl = G.nbake > 0 ? 16 : 8;
 	const char *lr = getenv("GG_PLAN_LREPL");
 
 	if (lr && atoi(lr) >= 1 && atoi(lr) <= 32)
@@ -180,24 +320,28 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	/* LDS budget: LREPL x slots x 2*naggs u64 must stay within
 	 * the per-block share; shrink replicas for wide agg lists */
 	{
-		int slots = nbake > 0 ? nbake : 32;
+		int slots = G.nbake > 0 ? G.nbake : 32;
 
 		while (lrepl > 1 &&
 		       (size_t) lrepl * slots * 2 * D.naggs * 8 > 64 * 1024)
 			lrepl /= 2;
 	}
-	std::snprintf(buf, sizeof(buf),
-		      "static_assert(sizeof(PlanDev) == %zu, \"layout\");\n"
-		      "#define LSLOTS 32\n#define LREPL %d\n"
-		      "#define LEMPTY ((long long) 0x8000000000000000ull)\n",
-		      sizeof(PlanDev), lrepl);
-	s += buf;
+	s += fmt("#define LREPL %d\n", lrepl);
 	/* fast (bounds-proven) aggregate values are exact in modular u64
 	 * arithmetic — the true per-row value is non-negative < 2^61, so
 	 * wrapping intermediates preserve the result and the int128
 	 * multiplies (3-4 u64 muls each) collapse to one mul per factor */
-	s += fast ? "#define VAT unsigned long long\n"
-		  : "#define VAT __int128\n";
+	s += G.fast ? "#define VAT unsigned long long\n"
+		    : "#define VAT __int128\n";
+	/* LW = u64 words per LDS accumulator.  fast (=proven by
+	 * plan.cpp's interval bound: every agg value non-negative and
+	 * bound*rows_per_block < 2^61) uses ONE word and fire-and-forget
+	 * LDS adds — the returned-value carry check otherwise makes
+	 * every add a RETURNING atomic, which serializes at the ~88
+	 * returning-atomics/us hot-word wall (measured: baked 2-word =
+	 * generic 5.5 ms; k_q1_agg's budget-proven 1-word form = 3.6 ms
+	 * on the same shape). */
+	s += G.fast ? "#define LW 1\n" : "#define LW 2\n";
 	{
 		bool nn = true;
 
@@ -210,94 +354,62 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		s += nn ? "#define AOK(a) true\n"
 			: "#define AOK(a) (aok[a])\n";
 	}
+	s += DEVICE_FNS;
+}
 
-	{
-		/* waves/SIMD occupancy hint; 4 matches the hand kernels,
-		 * sweepable (GG_PLAN_WAVES) — fewer waves = more VGPRs
-		 * per wave for the register-heavy baked tier */
-		int waves = 4;
-		const char *wv = getenv("GG_PLAN_WAVES");
+/* ---- per-row evaluation as a macro-free inline sequence ---- */
+static void emit_row_pass(std::string &s, const Gen &G)
+{
+	const PlanDev &D = G.D;
 
-		if (wv && atoi(wv) >= 1 && atoi(wv) <= 8)
-			waves = atoi(wv);
-		std::snprintf(buf, sizeof(buf),
-			      "extern \"C\" __global__ "
-			      "__launch_bounds__(256, %d)\n"
-			      "void plan_kernel(PlanDev P)\n{\n"
-			      "\tconst int64_t stride = "
-			      "(int64_t) gridDim.x * blockDim.x;\n", waves);
-		s += buf;
-	}
-
-	/* ---- per-row evaluation as a macro-free inline sequence ---- */
-	std::string rowfn;
-
-	rowfn += "\tauto row_pass = [&](int64_t i) -> bool\n\t{\n";
+	s += "\tauto row_pass = [&](int64_t i) -> bool\n\t{\n";
 	for (int p = 0; p < D.npreds; p++)
 	{
-		char d[32], ptr[64];
-
-		std::snprintf(d, sizeof(d), "v%d", p);
-		std::snprintf(ptr, sizeof(ptr), "P.preds[%d].col", p);
-		emit_ld(rowfn, d, ptr, D.preds[p].width, "i", nt);
+		emit_ld(s, fmt("v%d", p).c_str(),
+			fmt("P.preds[%d].col", p).c_str(), D.preds[p].width,
+			"i", G.nt);
 		if (D.preds[p].nulls)
-		{
-			std::snprintf(buf, sizeof(buf),
-				      "\t\tif (P.preds[%d].nulls[i]) return false;\n", p);
-			rowfn += buf;
-		}
-		std::snprintf(buf, sizeof(buf),
-			      "\t\tif (v%d < P.preds[%d].lo || v%d >= P.preds[%d].hi) return false;\n",
-			      p, p, p, p);
-		rowfn += buf;
+			s += fmt("\t\tif (P.preds[%d].nulls[i]) return false;\n",
+				 p);
+		s += fmt("\t\tif (v%d < P.preds[%d].lo || v%d >= P.preds[%d].hi) return false;\n",
+			 p, p, p, p);
 	}
 	for (int j = 0; j < D.njoins; j++)
 	{
 		if (D.joins[j].pnulls)
-		{
-			std::snprintf(buf, sizeof(buf),
-				      "\t\tif (P.joins[%d].pnulls[i]) return false;\n", j);
-			rowfn += buf;
-		}
-		char d[32], ptr[64];
-
-		std::snprintf(d, sizeof(d), "k%d", j);
-		std::snprintf(ptr, sizeof(ptr), "P.joins[%d].pkey", j);
-		emit_ld(rowfn, d, ptr, D.joins[j].width, "i");
+			s += fmt("\t\tif (P.joins[%d].pnulls[i]) return false;\n",
+				 j);
+		emit_ld(s, fmt("k%d", j).c_str(),
+			fmt("P.joins[%d].pkey", j).c_str(), D.joins[j].width,
+			"i");
 		if (D.joins[j].bits)
-		{
-			std::snprintf(buf, sizeof(buf),
-				      "\t\tif (k%d < 0 || k%d >= P.joins[%d].dlen ||\n"
-				      "\t\t    !((P.joins[%d].bits[k%d >> 6] >> (k%d & 63)) & 1))\n"
-				      "\t\t\treturn false;\n", j, j, j, j, j, j);
-			rowfn += buf;
-		}
+			s += fmt("\t\tif (k%d < 0 || k%d >= P.joins[%d].dlen ||\n"
+				 "\t\t    !((P.joins[%d].bits[k%d >> 6] >> (k%d & 63)) & 1))\n"
+				 "\t\t\treturn false;\n", j, j, j, j, j, j);
 		else
-		{
-			std::snprintf(buf, sizeof(buf),
-				      "\t\t{\n"
-				      "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
-				      "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
-				      "\t\t\tfor (;;) {\n"
-				      "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
-				      "\t\t\t\tif (cur == t) break;\n"
-				      "\t\t\t\tif (cur == 0) return false;\n"
-				      "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
-				      "\t\t\t}\n\t\t}\n", j, j, j, j, j);
-			rowfn += buf;
-		}
+			s += fmt("\t\t{\n"
+				 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
+				 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
+				 "\t\t\tfor (;;) {\n"
+				 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
+				 "\t\t\t\tif (cur == t) break;\n"
+				 "\t\t\t\tif (cur == 0) return false;\n"
+				 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
+				 "\t\t\t}\n\t\t}\n", j, j, j, j, j);
 	}
-	rowfn += "\t\treturn true;\n\t};\n";
-	s += rowfn;
+	s += "\t\treturn true;\n\t};\n";
+}
 
-	/* agg input values.  Factor-column loads are DEDUPLICATED at
-	 * generation time: the same device pointer can appear in many
-	 * aggregates (Q1 reads price in three sums) and clang cannot
-	 * prove P.aggs[i].col[f] aliases across aggs, so without this
-	 * the kernel issued 13 per-row VMEM loads where the
-	 * hand-written k_q1_agg issues 7 (measured via offline ISA
-	 * dump, tools/rtc_dump_local.cpp). */
-	std::string aggfn = "\tauto agg_vals = [&](int64_t i, VAT *av, bool *aok)\n\t{\n";
+/* agg input values.  Factor-column loads are DEDUPLICATED at
+ * generation time: the same device pointer can appear in many
+ * aggregates (Q1 reads price in three sums) and clang cannot
+ * prove P.aggs[i].col[f] aliases across aggs, so without this
+ * the kernel issued 13 per-row VMEM loads where the
+ * hand-written k_q1_agg issues 7 (measured via offline ISA
+ * dump, tools/rtc_dump_local.cpp). */
+static void emit_agg_vals(std::string &s, const Gen &G)
+{
+	const PlanDev &D = G.D;
 	std::vector<std::pair<const void *, int>> uniq;
 	auto var_of = [&](int a, int f) -> int
 	{
@@ -308,18 +420,23 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 			if (uniq[u].first == c && uniq[u].second == w)
 				return (int) u;
 		uniq.push_back({c, w});
-		{
-			char d[32], ptr[64];
-
-			std::snprintf(d, sizeof(d), "xu%d",
-				      (int) uniq.size() - 1);
-			std::snprintf(ptr, sizeof(ptr),
-				      "P.aggs[%d].col[%d]", a, f);
-			emit_ld(aggfn, d, ptr, w, "i", nt);
-		}
+		emit_ld(s, fmt("xu%d", (int) uniq.size() - 1).c_str(),
+			fmt("P.aggs[%d].col[%d]", a, f).c_str(), w, "i",
+			G.nt);
 		return (int) uniq.size() - 1;
 	};
+	/* the factor as it enters a product: the loaded var or its
+	 * (100±) term */
+	auto term_of = [&](int a, int f) -> std::string
+	{
+		int u = var_of(a, f);
 
+		return D.aggs[a].mod[f]
+			? fmt("xm%d_%d", u, (int) D.aggs[a].mod[f])
+			: fmt("xu%d", u);
+	};
+
+	s += "\tauto agg_vals = [&](int64_t i, VAT *av, bool *aok)\n\t{\n";
 	/* pass 1: one load per distinct (pointer, width) */
 	for (int a = 0; a < D.naggs; a++)
 		if (D.aggs[a].kind >= 2)
@@ -348,11 +465,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 					if (seen)
 						continue;
 					mods_done.push_back({u, m});
-					std::snprintf(buf, sizeof(buf),
-						      "\t\tint64_t xm%d_%d = 100 %c xu%d;\n",
-						      u, m,
-						      m == 1 ? '-' : '+', u);
-					aggfn += buf;
+					s += fmt("\t\tint64_t xm%d_%d = 100 %c xu%d;\n",
+						 u, m, m == 1 ? '-' : '+', u);
 				}
 	}
 	/* pass 2: per-agg strict flags + products over the shared vars */
@@ -360,515 +474,167 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	{
 		if (D.aggs[a].kind == 0)
 		{
-			std::snprintf(buf, sizeof(buf),
-				      "\t\tav[%d] = 1; aok[%d] = true;\n", a, a);
-			aggfn += buf;
+			s += fmt("\t\tav[%d] = 1; aok[%d] = true;\n", a, a);
 			continue;
 		}
-		std::snprintf(buf, sizeof(buf), "\t\taok[%d] = true;\n", a);
-		aggfn += buf;
+		s += fmt("\t\taok[%d] = true;\n", a);
 		for (int f = 0; f < D.aggs[a].nf; f++)
 			if (D.aggs[a].nulls[f])
-			{
-				std::snprintf(buf, sizeof(buf),
-					      "\t\tif (P.aggs[%d].nulls[%d][i]) aok[%d] = false;\n",
-					      a, f, a);
-				aggfn += buf;
-			}
+				s += fmt("\t\tif (P.aggs[%d].nulls[%d][i]) aok[%d] = false;\n",
+					 a, f, a);
 		if (D.aggs[a].kind == 1)
-		{
-			std::snprintf(buf, sizeof(buf), "\t\tav[%d] = 1;\n", a);
-			aggfn += buf;
-			continue;
-		}
-		if (D.aggs[a].kind >= 3)
-		{
+			s += fmt("\t\tav[%d] = 1;\n", a);
+		else if (D.aggs[a].kind >= 3)
 			/* MIN/MAX word: order-encode AFTER the modifier so
 			 * unsigned max combines both (MAX: x ^ msb, MIN:
 			 * its complement; 0 = identity = "no input") */
-			int u = var_of(a, 0);
-			char x[32];
-
-			if (D.aggs[a].mod[0])
-				std::snprintf(x, sizeof(x), "xm%d_%d", u,
-					      (int) D.aggs[a].mod[0]);
-			else
-				std::snprintf(x, sizeof(x), "xu%d", u);
-			std::snprintf(buf, sizeof(buf),
-				      "\t\tav[%d] = (VAT) %s((unsigned long long) %s"
-				      " ^ 0x8000000000000000ull);\n",
-				      a, D.aggs[a].kind == 3 ? "~" : "", x);
-			aggfn += buf;
-			continue;
-		}
-		std::snprintf(buf, sizeof(buf), "\t\t{ VAT v = 1;\n");
-		aggfn += buf;
-		for (int f = 0; f < D.aggs[a].nf; f++)
-		{
-			int u = var_of(a, f);
-
-			if (D.aggs[a].mod[f])
-				std::snprintf(buf, sizeof(buf),
-					      "\t\tv *= (VAT) xm%d_%d;\n",
-					      u, (int) D.aggs[a].mod[f]);
-			else
-				std::snprintf(buf, sizeof(buf),
-					      "\t\tv *= (VAT) xu%d;\n", u);
-			aggfn += buf;
-		}
-		std::snprintf(buf, sizeof(buf), "\t\tav[%d] = v; }\n", a);
-		aggfn += buf;
-	}
-	aggfn += "\t};\n";
-	s += aggfn;
-
-	/* Per-aggregate transition code, emitted only for plans holding a
-	 * MIN/MAX word.  The kinds are known here, so each accumulator gets
-	 * its own add or max and the row loop carries no kind branch.
-	 * Plans without such a word keep the uniform add loops below, so
-	 * their generated source does not change. */
-	bool has_mm = false;
-
-	for (int a = 0; a < D.naggs; a++)
-		if (D.aggs[a].kind >= 3)
-			has_mm = true;
-	/* av[a] into the accumulator at lo (and hi: empty = one-word
-	 * fast tier); MIN/MAX words use the non-returning unsigned max */
-	auto emit_atomic = [&](std::string &o, const char *ind, int a,
-			       const std::string &lo, const std::string &hi)
-	{
-		char b[1024];
-
-		if (D.aggs[a].kind >= 3)
-			std::snprintf(b, sizeof(b),
-				      "%sif (AOK(%d))\n%s\tatomicMax(&%s, "
-				      "(unsigned long long) av[%d]);\n",
-				      ind, a, ind, lo.c_str(), a);
-		else if (hi.empty())
-			std::snprintf(b, sizeof(b),
-				      "%sif (AOK(%d))\n%s\tatomicAdd(&%s, "
-				      "(unsigned long long) av[%d]);\n",
-				      ind, a, ind, lo.c_str(), a);
-		else
-			std::snprintf(b, sizeof(b),
-				      "%sif (AOK(%d))\n%s{\n"
-				      "%s\tunsigned long long vlo = (unsigned long long) av[%d];\n"
-				      "%s\tunsigned long long vhi = (unsigned long long) (av[%d] >> 64);\n"
-				      "%s\tunsigned long long old = atomicAdd(&%s, vlo);\n\n"
-				      "%s\tif (old + vlo < old)\n%s\t\tvhi++;\n"
-				      "%s\tif (vhi)\n%s\t\tatomicAdd(&%s, vhi);\n%s}\n",
-				      ind, a, ind, ind, a, ind, a, ind,
-				      lo.c_str(), ind, ind, ind, ind,
-				      hi.c_str(), ind);
-		o += b;
-	};
-	/* fold the LREPL replicas of accumulator a (words w0/w1 indexed by
-	 * rr; w1 empty = one-word tier) into the global slot `slot` */
-	auto emit_flush = [&](std::string &o, int a, const std::string &w0,
-			      const std::string &w1)
-	{
-		char b[1536];
-
-		if (D.aggs[a].kind >= 3)
-			std::snprintf(b, sizeof(b),
-				      "\t\t{\n\t\t\tunsigned long long m = 0;\n\n"
-				      "\t\t\tfor (int rr = 0; rr < LREPL; rr++)\n"
-				      "\t\t\t\tif (%s > m)\n\t\t\t\t\tm = %s;\n"
-				      "\t\t\tif (m)\n"
-				      "\t\t\t\tatomicMax(&P.tvals[(slot * NA + %d) * 2], m);\n"
-				      "\t\t}\n",
-				      w0.c_str(), w0.c_str(), a);
+			s += fmt("\t\tav[%d] = (VAT) %s((unsigned long long) %s"
+				 " ^ 0x8000000000000000ull);\n",
+				 a, D.aggs[a].kind == 3 ? "~" : "",
+				 term_of(a, 0).c_str());
 		else
 		{
-			char fold[512];
-
-			if (w1.empty())
-				std::snprintf(fold, sizeof(fold),
-					      "\t\t\t\tlo += %s;\n", w0.c_str());
-			else
-				std::snprintf(fold, sizeof(fold),
-					      "\t\t\t{\n"
-					      "\t\t\t\tunsigned long long rl = %s;\n"
-					      "\t\t\t\tunsigned long long o = lo;\n\n"
-					      "\t\t\t\tlo += rl;\n"
-					      "\t\t\t\thi += %s + (lo < o);\n"
-					      "\t\t\t}\n",
-					      w0.c_str(), w1.c_str());
-			std::snprintf(b, sizeof(b),
-				      "\t\t{\n\t\t\tunsigned long long lo = 0, hi = 0;\n\n"
-				      "\t\t\tfor (int rr = 0; rr < LREPL; rr++)\n%s"
-				      "\t\t\tif (lo || hi)\n\t\t\t{\n"
-				      "\t\t\t\tunsigned long long old =\n"
-				      "\t\t\t\t\tatomicAdd(&P.tvals[(slot * NA + %d) * 2], lo);\n\n"
-				      "\t\t\t\tif (old + lo < old)\n\t\t\t\t\thi++;\n"
-				      "\t\t\t\tif (hi)\n"
-				      "\t\t\t\t\tatomicAdd(&P.tvals[(slot * NA + %d) * 2 + 1], hi);\n"
-				      "\t\t\t}\n\t\t}\n",
-				      fold, a, a);
-		}
-		o += b;
-	};
-	auto idx = [](const char *fmt, int a) -> std::string
-	{
-		char b[128];
-
-		std::snprintf(b, sizeof(b), fmt, a);
-		return b;
-	};
-
-	/* NAGGS as a real constant for array bounds */
-	s += std::string("\tconstexpr int NA = ") +
-		std::to_string(D.naggs) + ";\n";
-
-	if (D.ngroup == 0)
-	{
-		s += R"GG(
-	unsigned long long alo[NA] = {};
-	long long ahi[NA] = {};
-
-	for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-	     i < P.n; i += stride)
-	{
-		if (!row_pass(i))
-			continue;
-		__int128 av[NA];
-		bool aok[NA];
-
-		agg_vals(i, av, aok);
-)GG";
-		if (has_mm)
-			for (int a = 0; a < D.naggs; a++)
-			{
-				if (D.aggs[a].kind >= 3)
-					std::snprintf(buf, sizeof(buf),
-						      "\t\tif (AOK(%d) && (unsigned long long) av[%d] > alo[%d])\n"
-						      "\t\t\talo[%d] = (unsigned long long) av[%d];\n",
-						      a, a, a, a, a);
-				else
-					std::snprintf(buf, sizeof(buf),
-						      "\t\tif (AOK(%d))\n\t\t{\n"
-						      "\t\t\tunsigned long long old = alo[%d];\n\n"
-						      "\t\t\talo[%d] += (unsigned long long) av[%d];\n"
-						      "\t\t\tahi[%d] += (long long) (av[%d] >> 64) + (alo[%d] < old);\n"
-						      "\t\t}\n",
-						      a, a, a, a, a, a, a);
-				s += buf;
-			}
-		else
-			s += R"GG(		for (int a = 0; a < NA; a++)
-		{
-			if (!AOK(a))
-				continue;
-			unsigned long long vlo = (unsigned long long) av[a];
-			unsigned long long old = alo[a];
-
-			alo[a] += vlo;
-			ahi[a] += (long long) (av[a] >> 64) + (alo[a] < old);
-		}
-)GG";
-		s += "\t}\n";
-		if (has_mm)
-			for (int a = 0; a < D.naggs; a++)
-			{
-				char rb[1024];
-
-				/* MIN/MAX word: wave max, one global max per
-				 * wave; the rest: wave add as in the uniform
-				 * loop */
-				if (D.aggs[a].kind >= 3)
-					std::snprintf(rb, sizeof(rb),
-						      "\tfor (int off = 32; off; off >>= 1)\n\t{\n"
-						      "\t\tunsigned long long o = __shfl_down(alo[%d], off, 64);\n\n"
-						      "\t\tif (o > alo[%d])\n\t\t\talo[%d] = o;\n\t}\n"
-						      "\tif ((threadIdx.x & 63) == 0 && alo[%d])\n"
-						      "\t\tatomicMax(&P.tvals[2 * %d], alo[%d]);\n",
-						      a, a, a, a, a, a);
-				else
-					std::snprintf(rb, sizeof(rb),
-						      "\tfor (int off = 32; off; off >>= 1)\n\t{\n"
-						      "\t\tunsigned long long olo = alo[%d];\n\n"
-						      "\t\talo[%d] += __shfl_down(alo[%d], off, 64);\n"
-						      "\t\tahi[%d] += __shfl_down(ahi[%d], off, 64) +\n"
-						      "\t\t\t(long long) (alo[%d] < olo);\n\t}\n"
-						      "\tif ((threadIdx.x & 63) == 0 && (alo[%d] || ahi[%d]))\n\t{\n"
-						      "\t\tunsigned long long old =\n"
-						      "\t\t\tatomicAdd(&P.tvals[2 * %d], alo[%d]);\n"
-						      "\t\tunsigned long long hi = (unsigned long long) ahi[%d] +\n"
-						      "\t\t\t(old + alo[%d] < old ? 1ull : 0ull);\n\n"
-						      "\t\tif (hi)\n"
-						      "\t\t\tatomicAdd(&P.tvals[2 * %d + 1], hi);\n\t}\n",
-						      a, a, a, a, a, a, a, a, a, a,
-						      a, a, a);
-				s += rb;
-			}
-		else
-			s += R"GG(	for (int a = 0; a < NA; a++)
-	{
-		for (int off = 32; off; off >>= 1)
-		{
-			unsigned long long olo = alo[a];
-
-			alo[a] += __shfl_down(alo[a], off, 64);
-			ahi[a] += __shfl_down(ahi[a], off, 64) +
-				(long long) (alo[a] < olo);
-		}
-		if ((threadIdx.x & 63) == 0 && (alo[a] || ahi[a]))
-		{
-			unsigned long long old =
-				atomicAdd(&P.tvals[2 * a], alo[a]);
-			unsigned long long hi = (unsigned long long) ahi[a] +
-				(old + alo[a] < old ? 1ull : 0ull);
-
-			if (hi)
-				atomicAdd(&P.tvals[2 * a + 1], hi);
+			s += "\t\t{ VAT v = 1;\n";
+			for (int f = 0; f < D.aggs[a].nf; f++)
+				s += fmt("\t\tv *= (VAT) %s;\n",
+					 term_of(a, f).c_str());
+			s += fmt("\t\tav[%d] = v; }\n", a);
 		}
 	}
-)GG";
-		s += R"GG(	if (blockIdx.x == 0 && threadIdx.x == 0)
-		P.tkeys[0] = 0;
+	s += "\t};\n";
 }
-)GG";
-	}
-	else
-	{
-		/* group code expression */
-		std::string gcode;
 
-		if (D.ngroup == 2)
-		{
-			gcode = "\t\tlong long e0 = ";
-			gcode += has_gnull0 ? "(P.gnulls[0][i] ? 256 : (long long) ((const uint8_t *) P.gcol[0])[i]);\n"
-					    : "(long long) ((const uint8_t *) P.gcol[0])[i];\n";
-			gcode += "\t\tlong long e1 = ";
-			gcode += has_gnull1 ? "(P.gnulls[1][i] ? 256 : (long long) ((const uint8_t *) P.gcol[1])[i]);\n"
-					    : "(long long) ((const uint8_t *) P.gcol[1])[i];\n";
-			gcode += "\t\tlong long code = e0 * 512 + e1;\n";
-		}
-		else
-		{
-			const char *ld = D.gwidth[0] == 1
-				? "(long long) ((const uint8_t *) P.gcol[0])[i]"
-				: D.gwidth[0] == 4
-				? "(long long) ((const int32_t *) P.gcol[0])[i]"
-				: "((const int64_t *) P.gcol[0])[i]";
+/* the scan loop's head, shared by every variant: filter, group code
+ * (grouped plans), aggregate inputs */
+static void emit_loop_head(std::string &s, const Gen &G)
+{
+	const PlanDev &D = G.D;
+	static const char *const ld[] = {
+		"(long long) ((const uint8_t *) P.gcol[%d])[i]",
+		"(long long) ((const int32_t *) P.gcol[%d])[i]",
+		"((const int64_t *) P.gcol[%d])[i]"};
 
-			gcode = "\t\tlong long code = ";
-			if (has_gnull0)
-			{
-				gcode += "P.gnulls[0][i] ? (long long) "
-					 "0x8000000000000001ull : (";
-				gcode += ld;
-				gcode += ");\n";
-			}
-			else
-			{
-				gcode += ld;
-				gcode += ";\n";
-			}
-		}
-
-		if (nbake > 0)
-		{
-			/* ---- baked-codes variant ----------------------
-			 * The group set was observed on a prior execute
-			 * of this plan (tables are immutable, so it is
-			 * exact for repeats).  Codes become a constexpr
-			 * compare chain -> direct LDS index: no key
-			 * probe, no CAS on the hot path.  A row whose
-			 * code is not baked (impossible for repeats,
-			 * kept for correctness) takes the global-table
-			 * path, and group PRESENCE is tracked in a
-			 * per-thread bit mask so groups whose sums are
-			 * all zero still materialize. */
-			s += "\tconstexpr int NG = " +
-				std::to_string(nbake) + ";\n"
-				"\tconstexpr long long GC[NG] = {";
-			for (int q = 0; q < nbake; q++)
-			{
-				std::snprintf(buf, sizeof(buf), "%s%lldll",
-					      q ? ", " : "", bake[q]);
-				s += buf;
-			}
-			s += "};\n";
-			/* LW = u64 words per accumulator.  fast (=proven
-			 * by plan.cpp's interval bound: every agg value
-			 * non-negative and bound*rows_per_block < 2^61)
-			 * uses ONE word and fire-and-forget LDS adds —
-			 * the returned-value carry check otherwise makes
-			 * every add a RETURNING atomic, which serializes
-			 * at the ~88 returning-atomics/us hot-word wall
-			 * (measured: baked 2-word = generic 5.5 ms;
-			 * k_q1_agg's budget-proven 1-word form = 3.6 ms
-			 * on the same shape). */
-			s += fast ? "#define LW 1\n" : "#define LW 2\n";
-			/* odd per-replica stride: spreads replicas across
-			 * LDS banks (k_q1_agg's Q1_STRIDE trick) */
-			s += "#define LPAD ((NG * LW * NA) | 1)\n";
-			s += R"GG(
-	__shared__ unsigned long long lvals[LREPL * LPAD];
-	__shared__ unsigned int btouch;
-
-	for (int q = threadIdx.x; q < LREPL * LPAD; q += blockDim.x)
-		lvals[q] = 0;
-	if (threadIdx.x == 0)
-		btouch = 0;
-	__syncthreads();
-	const int lrep = (int) (threadIdx.x & (LREPL - 1));
-	unsigned int tmask = 0;
-	unsigned int nmiss = 0;
-
-	auto gslot = [&](long long code) -> int64_t
-	{
-		uint64_t pos = (uint64_t) gg_hashint8(code) & (P.nslots - 1);
-
-		for (uint64_t it = 0; it < P.nslots; it++)
-		{
-			unsigned long long cur = P.tkeys[pos];
-
-			if (cur == (unsigned long long) code)
-				return (int64_t) pos;
-			if (cur == 0x8000000000000000ull)
-			{
-				unsigned long long prev = atomicCAS(
-					&P.tkeys[pos], 0x8000000000000000ull,
-					(unsigned long long) code);
-
-				if (prev == 0x8000000000000000ull ||
-				    prev == (unsigned long long) code)
-					return (int64_t) pos;
-				continue;
-			}
-			pos = (pos + 1) & (P.nslots - 1);
-		}
-		return -1;
-	};
-
+	s += R"GG(
 	for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	     i < P.n; i += stride)
 	{
 		if (!row_pass(i))
 			continue;
 )GG";
-			s += gcode;
-			s += R"GG(
+	if (D.ngroup == 2)
+	{
+		/* two char1 columns; NULL encodes as 256 */
+		for (int g = 0; g < 2; g++)
+		{
+			std::string e = fmt(ld[0], g);
+
+			if (G.gnull[g])
+				e = fmt("(P.gnulls[%d][i] ? 256 : %s)", g,
+					e.c_str());
+			s += fmt("\t\tlong long e%d = %s;\n", g, e.c_str());
+		}
+		s += "\t\tlong long code = e0 * 512 + e1;\n";
+	}
+	else if (D.ngroup == 1)
+	{
+		std::string e = fmt(ld[D.gwidth[0] == 1 ? 0
+				       : D.gwidth[0] == 4 ? 1 : 2], 0);
+
+		if (G.gnull[0])
+			e = "P.gnulls[0][i] ? (long long) "
+				"0x8000000000000001ull : (" + e + ")";
+		s += "\t\tlong long code = " + e + ";\n";
+	}
+	s += R"GG(
 		VAT av[NA];
 		bool aok[NA];
 
 		agg_vals(i, av, aok);
-		int g = -1;
-#pragma unroll
-		for (int q = 0; q < NG; q++)
-			if (code == GC[q])
-				g = q;
-		if (g >= 0)
-		{
-			unsigned long long *mine = &lvals[lrep * LPAD];
-
-			tmask |= 1u << g;
 )GG";
-			if (has_mm)
-				for (int a = 0; a < D.naggs; a++)
-					emit_atomic(s, "\t\t\t", a,
-						    idx(fast ? "mine[g * NA + %d]"
-							: "mine[(g * NA + %d) * 2]", a),
-						    fast ? std::string()
-						    : idx("mine[(g * NA + %d) * 2 + 1]",
-							  a));
-			else
-				s += R"GG(			for (int a = 0; a < NA; a++)
-			{
-				if (!AOK(a))
-					continue;
-#if LW == 1
-				atomicAdd(&mine[g * NA + a],
-					  (unsigned long long) av[a]);
-#else
-				unsigned long long vlo =
-					(unsigned long long) av[a];
-				unsigned long long vhi =
-					(unsigned long long) (av[a] >> 64);
-				unsigned long long old = atomicAdd(
-					&mine[(g * NA + a) * 2], vlo);
-
-				if (old + vlo < old)
-					vhi++;
-				if (vhi)
-					atomicAdd(&mine[(g * NA + a) * 2 + 1],
-						  vhi);
-#endif
-			}
-)GG";
-			s += R"GG(		}
-		else
-			/* a code outside the baked set is impossible on
-			 * re-execution over immutable tables; if it ever
-			 * happens, flag it and let the host re-run the
-			 * generic kernel (keeping the full global-table
-			 * path INSIDE this loop cost ~35% extra
-			 * instructions for a dead branch) */
-			nmiss++;
-	}
-	if (nmiss)
-		atomicOr(P.err, 2ull);
-	if (tmask)
-		atomicOr(&btouch, tmask);
-	__syncthreads();
-	for (int q = threadIdx.x; q < NG; q += blockDim.x)
-	{
-		if (!((btouch >> q) & 1u))
-			continue;
-		int64_t slot = gslot(GC[q]);
-
-		if (slot < 0) { atomicOr(P.err, 1ull); continue; }
-)GG";
-			if (has_mm)
-				for (int a = 0; a < D.naggs; a++)
-					emit_flush(s, a,
-						   idx(fast ? "lvals[rr * LPAD + q * NA + %d]"
-						       : "lvals[rr * LPAD + (q * NA + %d) * 2]", a),
-						   fast ? std::string()
-						   : idx("lvals[rr * LPAD + (q * NA + %d) * 2 + 1]",
-							 a));
-			else
-				s += R"GG(		for (int a = 0; a < NA; a++)
-		{
-#if LW == 1
-			unsigned long long lo = 0, hi = 0;
-
-			for (int rr = 0; rr < LREPL; rr++)
-				lo += lvals[rr * LPAD + q * NA + a];
-#else
-			unsigned long long lo = 0, hi = 0;
-
-			for (int rr = 0; rr < LREPL; rr++)
-			{
-				unsigned long long rl =
-					lvals[rr * LPAD + (q * NA + a) * 2];
-				unsigned long long o = lo;
-
-				lo += rl;
-				hi += lvals[rr * LPAD +
-					    (q * NA + a) * 2 + 1] + (lo < o);
-			}
-#endif
-			if (!lo && !hi)
-				continue;
-			unsigned long long old =
-				atomicAdd(&P.tvals[(slot * NA + a) * 2], lo);
-
-			if (old + lo < old)
-				hi++;
-			if (hi)
-				atomicAdd(&P.tvals[(slot * NA + a) * 2 + 1],
-					  hi);
-		}
-)GG";
-			s += R"GG(	}
 }
+
+/* where a row's transition lands */
+enum Dest
+{
+	DEST_REG,		/* registers alo[a] / ahi[a] */
+	DEST_LDS,		/* generic block cache lvals[lrep][ls][..] */
+	DEST_BAKED,		/* baked table mine[..], LW words */
+	DEST_GLOBAL		/* P.tvals[(slot * NA + a) * 2] */
+};
+
+/* av[a] into accumulator a at `dest`, once per accumulator from its
+ * kind: the kinds are known here, so the row loop carries no kind
+ * branch.  MIN/MAX words take the (non-returning) unsigned max, the
+ * one-word tier a fire-and-forget add, everything else the two-word
+ * add with carry. */
+static void emit_transitions(std::string &s, const Gen &G, const char *ind,
+			     Dest dest)
+{
+	static const char *const word0[] = {
+		"alo[%d]", "lvals[lrep][ls][2 * %d]",
+		"mine[(g * NA + %d) * LW]", "P.tvals[(slot * NA + %d) * 2]"};
+
+	for (int a = 0; a < G.D.naggs; a++)
+	{
+		std::string w = fmt(word0[dest], a);
+		std::string v = fmt("(unsigned long long) av[%d]", a);
+		std::string call;
+
+		if (G.D.aggs[a].kind >= 3)
+			call = dest == DEST_REG
+				? fmt("gg_max(%s, %s)", w.c_str(), v.c_str())
+				: fmt("atomicMax(&%s, %s)", w.c_str(), v.c_str());
+		else if (dest == DEST_BAKED && G.fast)
+			call = fmt("atomicAdd(&%s, %s)", w.c_str(), v.c_str());
+		else if (dest == DEST_REG)
+			call = fmt("gg_add2(%s, ahi[%d], %s, "
+				   "(unsigned long long) (av[%d] >> 64))",
+				   w.c_str(), a, v.c_str(), a);
+		else
+			call = fmt("gg_atomic_add2(&%s, %s, "
+				   "(unsigned long long) (av[%d] >> 64))",
+				   w.c_str(), v.c_str(), a);
+		s += fmt("%sif (AOK(%d))\n%s\t%s;\n", ind, a, ind,
+			 call.c_str());
+	}
+}
+
+/* fold the LREPL replicas of every accumulator of LDS group q (word0:
+ * accumulator a's first word in replica rr) into global slot `slot` */
+static void emit_flushes(std::string &s, const Gen &G, const char *word0)
+{
+	for (int a = 0; a < G.D.naggs; a++)
+		s += fmt("\t\tGG_FOLD_FLUSH_%s(&P.tvals[(slot * NA + %d) * 2], %s);\n",
+			 G.D.aggs[a].kind >= 3 ? "MAX" : "ADD", a,
+			 fmt(word0, a).c_str());
+}
+
+/* no group columns: register accumulators, one wave-reduced global
+ * atomic per wave and accumulator */
+static void emit_body_global(std::string &s, const Gen &G)
+{
+	s += "\tunsigned long long alo[NA] = {};\n"
+	     "\tunsigned long long ahi[NA] = {};\n";
+	emit_loop_head(s, G);
+	emit_transitions(s, G, "\t\t", DEST_REG);
+	s += "\t}\n";
+	for (int a = 0; a < G.D.naggs; a++)
+		if (G.D.aggs[a].kind >= 3)
+			s += fmt("\tgg_wave_flush_max(&P.tvals[2 * %d], alo[%d]);\n",
+				 a, a);
+		else
+			s += fmt("\tgg_wave_flush_add(&P.tvals[2 * %d], alo[%d], ahi[%d]);\n",
+				 a, a, a);
+	s += R"GG(	if (blockIdx.x == 0 && threadIdx.x == 0)
+		P.tkeys[0] = 0;
 )GG";
-			goto compile;
-		}
-		s += R"GG(
+}
+
+/* grouped, group set unknown: per-block LDS find-or-create cache in
+ * front of the global table */
+static void emit_body_grouped(std::string &s, const Gen &G)
+{
+	s += R"GG(
 	__shared__ long long lkeys[LSLOTS];
 	__shared__ unsigned long long lvals[LREPL][LSLOTS][2 * NA];
 
@@ -879,46 +645,9 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		((unsigned long long *) lvals)[q] = 0;
 	__syncthreads();
 	const int lrep = (int) (threadIdx.x & (LREPL - 1));
-
-	auto gslot = [&](long long code) -> int64_t
-	{
-		uint64_t pos = (uint64_t) gg_hashint8(code) & (P.nslots - 1);
-
-		for (uint64_t it = 0; it < P.nslots; it++)
-		{
-			unsigned long long cur = P.tkeys[pos];
-
-			if (cur == (unsigned long long) code)
-				return (int64_t) pos;
-			if (cur == 0x8000000000000000ull)
-			{
-				unsigned long long prev = atomicCAS(
-					&P.tkeys[pos], 0x8000000000000000ull,
-					(unsigned long long) code);
-
-				if (prev == 0x8000000000000000ull ||
-				    prev == (unsigned long long) code)
-					return (int64_t) pos;
-				continue;
-			}
-			pos = (pos + 1) & (P.nslots - 1);
-		}
-		return -1;
-	};
-
-	for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
-	     i < P.n; i += stride)
-	{
-		if (!row_pass(i))
-			continue;
 )GG";
-		s += gcode;
-		s += R"GG(
-		__int128 av[NA];
-		bool aok[NA];
-
-		agg_vals(i, av, aok);
-		int ls = -1;
+	emit_loop_head(s, G);
+	s += R"GG(		int ls = -1;
 		uint32_t pos = (uint32_t) gg_hashint8(code) & (LSLOTS - 1);
 
 		for (int probe = 0; probe < 8; probe++)
@@ -942,109 +671,108 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		if (ls >= 0)
 		{
 )GG";
-		if (has_mm)
-			for (int a = 0; a < D.naggs; a++)
-				emit_atomic(s, "\t\t\t", a,
-					    idx("lvals[lrep][ls][2 * %d]", a),
-					    idx("lvals[lrep][ls][2 * %d + 1]", a));
-		else
-			s += R"GG(			for (int a = 0; a < NA; a++)
-			{
-				if (!AOK(a))
-					continue;
-				unsigned long long vlo =
-					(unsigned long long) av[a];
-				unsigned long long vhi =
-					(unsigned long long) (av[a] >> 64);
-				unsigned long long old = atomicAdd(
-					&lvals[lrep][ls][2 * a], vlo);
-
-				if (old + vlo < old)
-					vhi++;
-				if (vhi)
-					atomicAdd(&lvals[lrep][ls][2 * a + 1],
-						  vhi);
-			}
-)GG";
-		s += R"GG(		}
+	emit_transitions(s, G, "\t\t\t", DEST_LDS);
+	s += R"GG(		}
 		else
 		{
-			int64_t slot = gslot(code);
+			int64_t slot = gg_slot(P, code);
 
 			if (slot < 0) { atomicOr(P.err, 1ull); continue; }
 )GG";
-		if (has_mm)
-			for (int a = 0; a < D.naggs; a++)
-				emit_atomic(s, "\t\t\t", a,
-					    idx("P.tvals[(slot * NA + %d) * 2]", a),
-					    idx("P.tvals[(slot * NA + %d) * 2 + 1]",
-						a));
-		else
-			s += R"GG(			for (int a = 0; a < NA; a++)
-			{
-				if (!AOK(a))
-					continue;
-				unsigned long long vlo =
-					(unsigned long long) av[a];
-				unsigned long long vhi =
-					(unsigned long long) (av[a] >> 64);
-				unsigned long long old = atomicAdd(
-					&P.tvals[(slot * NA + a) * 2], vlo);
-
-				if (old + vlo < old)
-					vhi++;
-				if (vhi)
-					atomicAdd(&P.tvals[(slot * NA + a) * 2 + 1],
-						  vhi);
-			}
-)GG";
-		s += R"GG(		}
+	emit_transitions(s, G, "\t\t\t", DEST_GLOBAL);
+	s += R"GG(		}
 	}
 	__syncthreads();
 	for (int q = threadIdx.x; q < LSLOTS; q += blockDim.x)
 	{
 		if (lkeys[q] == LEMPTY)
 			continue;
-		int64_t slot = gslot(lkeys[q]);
+		int64_t slot = gg_slot(P, lkeys[q]);
 
 		if (slot < 0) { atomicOr(P.err, 1ull); continue; }
 )GG";
-		if (has_mm)
-			for (int a = 0; a < D.naggs; a++)
-				emit_flush(s, a, idx("lvals[rr][q][2 * %d]", a),
-					   idx("lvals[rr][q][2 * %d + 1]", a));
-		else
-			s += R"GG(		for (int a = 0; a < NA; a++)
-		{
-			unsigned long long lo = 0, hi = 0;
-
-			for (int rr = 0; rr < LREPL; rr++)
-			{
-				unsigned long long rl = lvals[rr][q][2 * a];
-				unsigned long long o = lo;
-
-				lo += rl;
-				hi += lvals[rr][q][2 * a + 1] + (lo < o);
-			}
-			if (!lo && !hi)
-				continue;
-			unsigned long long old =
-				atomicAdd(&P.tvals[(slot * NA + a) * 2], lo);
-
-			if (old + lo < old)
-				hi++;
-			if (hi)
-				atomicAdd(&P.tvals[(slot * NA + a) * 2 + 1],
-					  hi);
-		}
-)GG";
-		s += R"GG(	}
+	emit_flushes(s, G, "lvals[rr][q][2 * %d]");
+	s += "\t}\n";
 }
-)GG";
-	}
 
-	/* ---- compile ---- */
-compile:;
+/* ---- baked-codes variant ----------------------
+ * The group set was observed on a prior execute
+ * of this plan (tables are immutable, so it is
+ * exact for repeats).  Codes become a constexpr
+ * compare chain -> direct LDS index: no key
+ * probe, no CAS on the hot path.  A row whose
+ * code is not baked (impossible for repeats,
+ * kept for correctness) is counted and the host
+ * re-runs the generic kernel, and group PRESENCE
+ * is tracked in a per-thread bit mask so groups
+ * whose sums are all zero still materialize. */
+static void emit_body_baked(std::string &s, const Gen &G)
+{
+	s += "\tconstexpr int NG = " + std::to_string(G.nbake) + ";\n"
+		"\tconstexpr long long GC[NG] = {";
+	for (int q = 0; q < G.nbake; q++)
+		s += fmt("%s%lldll", q ? ", " : "", G.bake[q]);
+	s += "};\n";
+	/* odd per-replica stride: spreads replicas across
+	 * LDS banks (k_q1_agg's Q1_STRIDE trick) */
+	s += "#define LPAD ((NG * LW * NA) | 1)\n";
+	s += R"GG(
+	__shared__ unsigned long long lvals[LREPL * LPAD];
+	__shared__ unsigned int btouch;
+
+	for (int q = threadIdx.x; q < LREPL * LPAD; q += blockDim.x)
+		lvals[q] = 0;
+	if (threadIdx.x == 0)
+		btouch = 0;
+	__syncthreads();
+	const int lrep = (int) (threadIdx.x & (LREPL - 1));
+	unsigned int tmask = 0;
+	unsigned int nmiss = 0;
+)GG";
+	emit_loop_head(s, G);
+	s += R"GG(		int g = -1;
+#pragma unroll
+		for (int q = 0; q < NG; q++)
+			if (code == GC[q])
+				g = q;
+		if (g >= 0)
+		{
+			unsigned long long *mine = &lvals[lrep * LPAD];
+
+			tmask |= 1u << g;
+)GG";
+	emit_transitions(s, G, "\t\t\t", DEST_BAKED);
+	s += R"GG(		}
+		else
+			/* a code outside the baked set is impossible on
+			 * re-execution over immutable tables; if it ever
+			 * happens, flag it and let the host re-run the
+			 * generic kernel (keeping the full global-table
+			 * path INSIDE this loop cost ~35% extra
+			 * instructions for a dead branch) */
+			nmiss++;
+	}
+	if (nmiss)
+		atomicOr(P.err, 2ull);
+	if (tmask)
+		atomicOr(&btouch, tmask);
+	__syncthreads();
+	for (int q = threadIdx.x; q < NG; q += blockDim.x)
+	{
+		if (!((btouch >> q) & 1u))
+			continue;
+		int64_t slot = gg_slot(P, GC[q]);
+
+		if (slot < 0) { atomicOr(P.err, 1ull); continue; }
+)GG";
+	emit_flushes(s, G, "lvals[rr * LPAD + (q * NA + %d) * LW]");
+	s += "\t}\n";
+}
+
+static gg_status
+compile_and_load(const std::string &src, int nbake,
+		 std::shared_ptr<void> *out)
+{
 	const char *dump = getenv("GG_PLAN_RTC_DUMP");
 
 	if (dump && dump[0])
@@ -1054,13 +782,13 @@ compile:;
 		if (f)
 		{
 			fprintf(f, "/* ==== nbake=%d ==== */\n%s",
-				nbake, s.c_str());
+				nbake, src.c_str());
 			fclose(f);
 		}
 	}
 	hiprtcProgram prog;
 
-	if (hiprtcCreateProgram(&prog, s.c_str(), "gg_plan.cu", 0, nullptr,
+	if (hiprtcCreateProgram(&prog, src.c_str(), "gg_plan.cu", 0, nullptr,
 				nullptr) != HIPRTC_SUCCESS)
 		return fail(GG_ENOTSUP, "hiprtcCreateProgram failed");
 	const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17"};
@@ -1093,6 +821,59 @@ compile:;
 		return fail(GG_ENOTSUP, "plan rtc function lookup failed");
 	*out = rtc;
 	return GG_OK;
+}
+
+/* generate + compile; returns GG_OK with *out set, or non-OK (caller
+ * falls back to the interpreted kernel) */
+gg_status
+plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
+		 std::shared_ptr<void> *out, const long long *bake,
+		 int nbake, bool fast)
+{
+	const char *dis = getenv("GG_PLAN_RTC");
+
+	if (dis && dis[0] == '0')
+		return fail(GG_ENOTSUP, "rtc disabled");
+	if (nbake <= 0)
+		fast = false;	/* the u64 fast tier exists only baked */
+
+	/* NT loads: measured FLAT while the row loop carried the dead
+	 * fallback (4.90 vs 4.96 ms, r02k) but +12% once the loop got
+	 * lean (4.20 -> 3.76 ms, r02nt2) — same physics as k_q1_agg's
+	 * +11%.  Default ON for baked kernels; GG_PLAN_RTC_NT=0 reverts. */
+	const char *ntv = getenv("GG_PLAN_RTC_NT");
+	bool nt = nbake > 0 && !(ntv && ntv[0] == '0');
+	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt};
+	std::string s;
+
+	emit_prelude(s, G);
+	{
+		/* waves/SIMD occupancy hint; 4 matches the hand kernels,
+		 * sweepable (GG_PLAN_WAVES) — fewer waves = more VGPRs
+		 * per wave for the register-heavy baked tier */
+		int waves = 4;
+		const char *wv = getenv("GG_PLAN_WAVES");
+
+		if (wv && atoi(wv) >= 1 && atoi(wv) <= 8)
+			waves = atoi(wv);
+		s += fmt("extern \"C\" __global__ "
+			 "__launch_bounds__(256, %d)\n"
+			 "void plan_kernel(PlanDev P)\n{\n"
+			 "\tconst int64_t stride = "
+			 "(int64_t) gridDim.x * blockDim.x;\n"
+			 /* NAGGS as a real constant for array bounds */
+			 "\tconstexpr int NA = %d;\n", waves, D.naggs);
+	}
+	emit_row_pass(s, G);
+	emit_agg_vals(s, G);
+	if (D.ngroup == 0)
+		emit_body_global(s, G);
+	else if (nbake > 0)
+		emit_body_baked(s, G);
+	else
+		emit_body_grouped(s, G);
+	s += "}\n";
+	return compile_and_load(s, nbake, out);
 }
 
 gg_status

@@ -14,6 +14,9 @@ Engine.execute_plan returns: sorted (key0, key1, vals), one vals entry
 per descriptor aggregate — int for COUNT/SUM, int or None for MIN/MAX,
 (sum, count) for AVG.
 """
+import contextlib
+import os
+
 import numpy as np
 
 NULL_KEY = -(1 << 63) + 1
@@ -121,3 +124,33 @@ def canon(groups):
     survive a JSON round trip the same way)."""
     return [[k0, k1, [list(v) if isinstance(v, tuple) else v
                       for v in vals]] for k0, k1, vals in groups]
+
+
+@contextlib.contextmanager
+def plan_mode(mode):
+    """GG_PLAN_RTC=0 routes a plan to the interpreted kernel; the
+    choice is made at the plan's first execute."""
+    if mode == "interp":
+        os.environ["GG_PLAN_RTC"] = "0"
+    try:
+        yield
+    finally:
+        os.environ.pop("GG_PLAN_RTC", None)
+
+
+def run(eng, mode, t, data, nulls, preds, group_cols, aggs, repeats=1,
+        exp=None):
+    n = len(next(iter(data.values())))
+    if exp is None:
+        exp = eval_plan(n, data, nulls, preds, [], group_cols, aggs)
+    with plan_mode(mode):
+        p = eng.compile_plan(t, preds=preds, group_cols=group_cols,
+                             aggs=aggs)
+        for r in range(repeats):
+            got = sorted(eng.execute_plan(p, max_groups=1 << 12),
+                         key=lambda g: (g[0], g[1]))
+            assert len(got) == len(exp), (r, len(got), len(exp))
+            for g, e in zip(got, exp):
+                assert (g[0], g[1]) == (e[0], e[1]), (r, g, e)
+                assert g[2] == e[2], (r, g, e)
+    return p, exp

@@ -11,14 +11,11 @@ MIN), encoding after the 100±col modifier, every accumulator tier
 (registers, block LDS cache, global-table overflow, baked 1-word and
 2-word tables) and the 4-way strided row loop.
 """
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import pyoracle
-from plan_minmax_ref import NEG_INF, eval_plan, register
+from plan_minmax_ref import NEG_INF, eval_plan, register, run
 
 pytestmark = pytest.mark.gpu
 
@@ -40,36 +37,6 @@ def eng():
 @pytest.fixture(params=["rtc", "interp"])
 def mode(request):
     return request.param
-
-
-@contextlib.contextmanager
-def plan_mode(mode):
-    """GG_PLAN_RTC=0 routes a plan to the interpreted kernel; the
-    choice is made at the plan's first execute."""
-    if mode == "interp":
-        os.environ["GG_PLAN_RTC"] = "0"
-    try:
-        yield
-    finally:
-        os.environ.pop("GG_PLAN_RTC", None)
-
-
-def run(eng, mode, t, data, nulls, preds, group_cols, aggs, repeats=1,
-        exp=None):
-    n = len(next(iter(data.values())))
-    if exp is None:
-        exp = eval_plan(n, data, nulls, preds, [], group_cols, aggs)
-    with plan_mode(mode):
-        p = eng.compile_plan(t, preds=preds, group_cols=group_cols,
-                             aggs=aggs)
-        for r in range(repeats):
-            got = sorted(eng.execute_plan(p, max_groups=1 << 12),
-                         key=lambda g: (g[0], g[1]))
-            assert len(got) == len(exp), (r, len(got), len(exp))
-            for g, e in zip(got, exp):
-                assert (g[0], g[1]) == (e[0], e[1]), (r, g, e)
-                assert g[2] == e[2], (r, g, e)
-    return p, exp
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 300])

@@ -4,6 +4,11 @@
  * CPU-only box, which is fine — the dump is what we want.  Test/dev
  * tooling only; never part of the product path.
  *
+ * Build (after the engine library):
+ *   hipcc -x c++ -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
+ *     tools/rtc_dump_local.cpp -o tools/rtc_dump_local
+ *     -Lgreengage_amd -lgreengage_engine -Wl,-rpath,$PWD/greengage_amd
+ *     -L/opt/rocm/lib -lamdhip64
  * Usage: rtc_dump_local [DUMPFILE [SHAPE]]
  *   q1     Q1-shaped grouped plan: generic + baked fast tier (default)
  *   q1w    same, baked 2-word tier
@@ -11,12 +16,21 @@
  *   q1mm   Q1-shaped with MIN/MAX/AVG lowered slots, baked fast tier
  *   q1mmw  same, baked 2-word tier
  *   q6mm   global-group plan with MIN/MAX/AVG lowered slots
+ *   gn8    one nullable 8-byte group column; generic + baked 2-word
+ *   g4     one 4-byte group column; generic + baked fast tier
+ *   join   global-group plan probing one bitmap join and one hash join
+ *          with a nullable probe key
+ *   pnull  global-group plan with a nullable predicate column
+ *   lrepl  q1mmw's 8 two-word aggregates under GG_PLAN_LREPL=32, which
+ *          the LDS budget shrinks back to 16 replicas
+ *   all    every shape above, DUMPFILE used as a prefix: <prefix><shape>.cu
  * Exit status is non-zero when a variant fails to COMPILE (a module
  * load / function lookup failure without a GPU is not a failure). */
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
 
 #include "../greengage_amd/csrc/engine_internal.h"
 
@@ -121,6 +135,26 @@ shape_q6(PlanDev &D, bool mm)
 	}
 }
 
+/* one group column of the given width: count, sum(qty), sum(price*disc) */
+static void
+shape_g1(PlanDev &D, int width, bool nullable)
+{
+	static const int c_q[] = {QTY}, c_pd[] = {PRICE, DISC};
+	static const int m_id[] = {0, 0, 0};
+
+	shape_q1(D, false);
+	D.ngroup = 1;
+	D.gcol[1] = nullptr;
+	D.gwidth[0] = width;
+	D.gwidth[1] = 0;
+	if (nullable)
+		D.gnulls[0] = (const uint8_t *) dummy + 136;
+	D.naggs = 3;
+	set_agg(D, 0, 0, 0, nullptr, nullptr);
+	set_agg(D, 1, 2, 1, c_q, m_id);
+	set_agg(D, 2, 2, 2, c_pd, m_id);
+}
+
 /* compile errors come back as GG_ENOTSUP with this message prefix */
 static bool
 compiled(gg_status s)
@@ -129,44 +163,117 @@ compiled(gg_status s)
 		!std::strstr(gg_engine_last_error(), "compile failed");
 }
 
-int
-main(int argc, char **argv)
+/* generic kernel, then (nbake > 0) the baked one appended to the dump */
+static bool
+dump_shape(const char *shape, const char *file)
 {
-	const char *shape = argc > 2 ? argv[2] : "q1";
+	static const long long q1codes[6] = {16710, 20038, 20050, 33350,
+		36934, 33347};
+	static const long long g1codes[3] = {3, 1000000007ll,
+		GG_PLAN_NULL_KEY};
 	bool mm = std::strstr(shape, "mm") != nullptr;
 	bool wide = shape[std::strlen(shape) - 1] == 'w';
-
-	setenv("GG_PLAN_RTC_DUMP", argc > 1 ? argv[1] : "/tmp/rtc_dump.cu",
-	       0);
-
+	const long long *codes = nullptr;
+	int nbake = 0;
 	PlanDev D{};
 	std::shared_ptr<void> out;
-	bool ok = true;
 
+	setenv("GG_PLAN_RTC_DUMP", file, 1);
+	unsetenv("GG_PLAN_LREPL");
 	if (!std::strncmp(shape, "q6", 2))
-	{
 		shape_q6(D, mm);
-		gg_status s1 = plan_rtc_compile(D, false, false, &out);
+	else if (!std::strncmp(shape, "q1", 2))
+	{
+		shape_q1(D, mm);
+		codes = q1codes;
+		nbake = 6;
+	}
+	else if (!std::strcmp(shape, "gn8") || !std::strcmp(shape, "g4"))
+	{
+		bool n8 = shape[1] == 'n';
 
-		ok = compiled(s1);
-		fprintf(stderr, "%s generic rc=%d\n", shape, s1);
+		shape_g1(D, n8 ? 8 : 4, n8);
+		wide = n8;
+		codes = g1codes;
+		nbake = n8 ? 3 : 2;
+	}
+	else if (!std::strcmp(shape, "join"))
+	{
+		shape_q6(D, false);
+		D.njoins = 2;
+		D.joins[0].pkey = dummy + 144;
+		D.joins[0].width = 8;
+		D.joins[0].bits = (const unsigned long long *) (dummy + 152);
+		D.joins[0].dlen = 1000;
+		D.joins[1].pkey = dummy + 160;
+		D.joins[1].pnulls = (const uint8_t *) dummy + 168;
+		D.joins[1].width = 4;
+		D.joins[1].hkeys = (const unsigned long long *) (dummy + 176);
+		D.joins[1].hslots = 1024;
+	}
+	else if (!std::strcmp(shape, "pnull"))
+	{
+		shape_q6(D, false);
+		D.preds[1].nulls = (const uint8_t *) dummy + 184;
+	}
+	else if (!std::strcmp(shape, "lrepl"))
+	{
+		setenv("GG_PLAN_LREPL", "32", 1);
+		shape_q1(D, true);
+		wide = true;
+		codes = q1codes;
+		nbake = 6;
 	}
 	else
 	{
-		long long codes[6] = {16710, 20038, 20050, 33350, 36934,
-			33347};
+		fprintf(stderr, "unknown shape %s\n", shape);
+		return false;
+	}
 
-		shape_q1(D, mm);
-		gg_status s1 = plan_rtc_compile(D, false, false, &out);
+	bool gn0 = D.gnulls[0] != nullptr;
+	gg_status s1 = plan_rtc_compile(D, gn0, false, &out);
+	bool ok = compiled(s1);
 
-		ok = compiled(s1);
-		gg_status s2 = plan_rtc_compile(D, false, false, &out, codes,
-						6, !wide);
+	if (!ok)
+		fprintf(stderr, "%s generic: %s\n", shape,
+			gg_engine_last_error());
+	if (nbake)
+	{
+		gg_status s2 = plan_rtc_compile(D, gn0, false, &out, codes,
+						nbake, !wide);
 
-		ok = ok && compiled(s2);
+		if (!compiled(s2))
+		{
+			fprintf(stderr, "%s baked: %s\n", shape,
+				gg_engine_last_error());
+			ok = false;
+		}
 		fprintf(stderr, "%s generic rc=%d baked-%s rc=%d\n", shape,
 			s1, wide ? "2word" : "fast", s2);
 	}
+	else
+		fprintf(stderr, "%s generic rc=%d\n", shape, s1);
+	return ok;
+}
+
+int
+main(int argc, char **argv)
+{
+	static const char *const all[] = {"q1", "q1w", "q6", "q1mm", "q1mmw",
+		"q6mm", "gn8", "g4", "join", "pnull", "lrepl"};
+	const char *file = argc > 1 ? argv[1] : "/tmp/rtc_dump.cu";
+	const char *shape = argc > 2 ? argv[2] : "q1";
+	bool ok = true;
+
+	if (!std::strcmp(shape, "all"))
+		for (const char *sh : all)
+		{
+			std::string f = std::string(file) + sh + ".cu";
+
+			ok = dump_shape(sh, f.c_str()) && ok;
+		}
+	else
+		ok = dump_shape(shape, file);
 	fprintf(stderr, "last error: %s\n(a module-load failure is expected "
 		"without a GPU)\n", gg_engine_last_error());
 	return ok ? 0 : 1;
