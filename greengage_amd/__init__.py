@@ -9,6 +9,8 @@ unloadable engine library raises immediately.
 from .engine import (  # noqa: F401
     Engine,
     EngineError,
+    JOIN_INNER,
+    JOIN_SEMI,
     PGDate,
     pgdate,
 )

@@ -586,6 +586,14 @@ struct PlanJoinDev
 	uint64_t hslots;
 };
 
+/* dense index map "no build row"; INNER build sides stay below it */
+#define PL_NOROW 0xFFFFFFFFu
+/* bits of the plan error word (PlanDev.err) */
+#define PL_ERR_FULL 1ull	/* group table full */
+#define PL_ERR_BAKE_MISS 2ull	/* baked kernel met an unbaked code */
+#define PL_ERR_DUP_KEY 4ull	/* INNER build key not unique, INT64_MIN or
+				 * outside the dense map */
+
 /* One device accumulator slot (two u64 words).  kind 0..2 are the
  * descriptor's COUNT(*) / COUNT(factors non-NULL) / SUM; plan.cpp
  * lowers MIN, MAX and AVG onto these plus two order-encoded kinds:
@@ -604,6 +612,27 @@ struct PlanAggDev
 	int8_t mod[3];		/* gg_plan_fmod */
 };
 
+/* What INNER joins add to a plan, kept in ONE block at the end of
+ * PlanDev: every field a plan without an INNER join reads keeps the
+ * offset it always had, so those plans' kernels stay the binaries they
+ * were (the interpreted kernel reads its descriptor through scalar
+ * loads in the row loop and was measurably slower on the Q1 shape when
+ * the join and aggregate entries merely grew: DESIGN.md, "Inner joins
+ * with payload columns").  Sources: 0 = the driving
+ * table, 1+k = the build table of INNER join k. */
+struct PlanPayloadDev
+{
+	/* INNER join j: key -> build-row-index map instead of a membership
+	 * set (joins[j].bits stays NULL).  joins[j].dlen > 0: dense,
+	 * jidx[j][key], PL_NOROW = absent; else jidx[j][] runs parallel to
+	 * joins[j].hkeys[], written only where a key was installed */
+	const uint32_t *jidx[GG_PLAN_MAX_JOINS];
+	int8_t jkind[GG_PLAN_MAX_JOINS];	/* gg_plan_joinkind */
+	int8_t jpsrc[GG_PLAN_MAX_JOINS];	/* source of joins[j].pkey */
+	int8_t gsrc[2];				/* source of gcol[g] */
+	int8_t asrc[GG_PLAN_MAX_AGGS][3];	/* source of aggs[a].col[f] */
+};
+
 struct PlanDev
 {
 	int64_t n;
@@ -618,6 +647,7 @@ struct PlanDev
 	uint64_t nslots;
 	unsigned long long *err;
 	PlanAggDev aggs[GG_PLAN_MAX_AGGS];
+	PlanPayloadDev pl;
 };
 
 struct PlanBuildDev
@@ -632,6 +662,9 @@ struct PlanBuildDev
 	int64_t dlen;
 	unsigned long long *hkeys;
 	uint64_t hslots;
+	uint32_t *idx;		/* INNER: row-index map (PlanPayloadDev.jidx) */
+	int kind;		/* gg_plan_joinkind */
+	unsigned long long *err;	/* plan error word (PL_ERR_DUP_KEY) */
 };
 
 /* blocks of 256 threads for n rows, clamped to [1, 2048]: the grid of

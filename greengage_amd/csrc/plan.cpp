@@ -39,10 +39,13 @@ struct PlanResolved
 	{
 		PlanBuildDev bd;	/* preds/key resolved; bits/hkeys
 					 * filled per execute (scratch) */
-		int64_t dlen;		/* >0: dense bitmap path */
-		uint64_t hslots;	/* else: hash set */
+		int64_t dlen;		/* >0: dense bitmap / index map */
+		uint64_t hslots;	/* else: hash set / key->index map */
 	};
 	std::vector<BJoin> joins;
+	/* rows of each column source: [0] driving table, [1+k] the build
+	 * table of join k */
+	int64_t src_rows[1 + GG_PLAN_MAX_JOINS] = {};
 	int64_t scan_rows = 0;
 	int64_t pred_bytes_per_row = 0;
 	/* hipRTC-specialized kernel (nullptr = interpreted fallback);
@@ -99,6 +102,40 @@ resolve_pred(Table *t, const gg_plan_pred *in, PlanPredDev *out)
 	return GG_OK;
 }
 
+extern "C" size_t
+gg_engine_plan_desc_size(void)
+{
+	return sizeof(gg_plan_desc);
+}
+
+/* the table a column source names (engine_abi.h "column sources"):
+ * 0 = the driving table, 1+k = the build table of INNER join k, where
+ * k < limit (njoins, or the probing join's own index for a probe_src) */
+static gg_status
+resolve_src(const gg_plan_desc *d, Table *scan, int src, int limit,
+	    const char *field, int at, Table **out)
+{
+	if (src == 0)
+	{
+		*out = scan;
+		return GG_OK;
+	}
+	if (src < 0 || src > d->njoins)
+		return fail(GG_EINVAL, "plan: %s %d names source %d, the plan "
+			    "has %d joins", field, at, src, d->njoins);
+	if (src > limit)
+		return fail(GG_EINVAL, "plan: %s %d names source %d, not an "
+			    "earlier join", field, at, src);
+	if (d->joins[src - 1].kind != GG_JOIN_INNER)
+		return fail(GG_EINVAL, "plan: %s %d names source %d, a SEMI "
+			    "join (no payload)", field, at, src);
+	*out = engine_table(d->joins[src - 1].build.table);
+	if (!*out)
+		return fail(GG_EINVAL, "plan: bad build table (join %d)",
+			    src - 1);
+	return GG_OK;
+}
+
 extern "C" gg_status
 gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 {
@@ -125,6 +162,7 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 	std::memset(&R->dev, 0, sizeof(R->dev));
 	R->dev.n = scan->nrows;
 	R->scan_rows = scan->nrows;
+	R->src_rows[0] = scan->nrows;
 	R->dev.npreds = d->scan.npreds;
 	for (int i = 0; i < d->scan.npreds; i++)
 	{
@@ -135,6 +173,22 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 			return st;
 		R->pred_bytes_per_row += R->dev.preds[i].width;
 	}
+
+	/* pred_bytes_per_row, the algorithmic figure: a driving column
+	 * counts at its width wherever it is read, as always; a payload
+	 * column (source != 0) counts once per plan however many aggregates
+	 * read it, plus 4 bytes per INNER join for the row index */
+	std::vector<std::pair<const void *, int>> payload_seen;
+	auto col_bytes = [&](const void *col, int src, int width) -> int
+	{
+		if (src == 0)
+			return width;
+		for (auto &q : payload_seen)
+			if (q.first == col && q.second == src)
+				return 0;
+		payload_seen.push_back({col, src});
+		return width;
+	};
 
 	R->dev.njoins = d->njoins;
 	for (int j = 0; j < d->njoins; j++)
@@ -148,13 +202,26 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		if (J->build.npreds < 0 ||
 		    J->build.npreds > GG_PLAN_MAX_PREDS)
 			return fail(GG_ENOTSUP, "plan: join %d pred count", j);
+		if (J->kind != GG_JOIN_SEMI && J->kind != GG_JOIN_INNER)
+			return fail(GG_ENOTSUP, "plan: join %d kind", j);
+		if (J->kind == GG_JOIN_INNER && bt->nrows >= 0xFFFFFFFFll)
+			return fail(GG_ENOTSUP, "plan: join %d: INNER build "
+				    "side of %lld rows (32-bit row indices)", j,
+				    (long long) bt->nrows);
+		Table *pt = nullptr;
+
+		GG_TRY(resolve_src(d, scan, J->probe_src, j, "probe_src", j,
+				   &pt));
 		Table::Col *bk = bt->find(J->build_key ? J->build_key : "");
-		Table::Col *pk = scan->find(J->probe_key ? J->probe_key : "");
+		Table::Col *pk = pt->find(J->probe_key ? J->probe_key : "");
 
 		if (!bk || !pk)
 			return fail(GG_EINVAL,
 				    "plan: join %d key column missing", j);
 		PlanResolved::BJoin bj{};
+
+		bj.bd.kind = J->kind;
+		R->src_rows[1 + j] = bt->nrows;
 
 		bj.bd.key = bk->dev;
 		bj.bd.knulls = (const uint8_t *) bk->nulls;
@@ -173,14 +240,24 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		R->dev.joins[j].pkey = pk->dev;
 		R->dev.joins[j].pnulls = (const uint8_t *) pk->nulls;
 		R->dev.joins[j].width = coltype_width(pk->type);
-		R->pred_bytes_per_row += R->dev.joins[j].width;
+		R->dev.pl.jkind[j] = (int8_t) J->kind;
+		R->dev.pl.jpsrc[j] = J->probe_src;
+		/* the probe key, plus the gathered 4-byte row index */
+		R->pred_bytes_per_row +=
+			col_bytes(pk->dev, J->probe_src,
+				  R->dev.joins[j].width) +
+			(J->kind == GG_JOIN_INNER ? 4 : 0);
 	}
 
 	R->dev.ngroup = d->ngroup;
 	for (int g = 0; g < d->ngroup; g++)
 	{
-		Table::Col *c = scan->find(d->group_cols[g]
-					   ? d->group_cols[g] : "");
+		Table *gt = nullptr;
+
+		GG_TRY(resolve_src(d, scan, d->group_src[g], d->njoins,
+				   "group_src", g, &gt));
+		Table::Col *c = gt->find(d->group_cols[g]
+					 ? d->group_cols[g] : "");
 
 		if (!c)
 			return fail(GG_EINVAL, "plan: group column missing");
@@ -190,7 +267,9 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		R->dev.gcol[g] = c->dev;
 		R->dev.gnulls[g] = (const uint8_t *) c->nulls;
 		R->dev.gwidth[g] = coltype_width(c->type);
-		R->pred_bytes_per_row += R->dev.gwidth[g];
+		R->dev.pl.gsrc[g] = d->group_src[g];
+		R->pred_bytes_per_row += col_bytes(c->dev, d->group_src[g],
+						   R->dev.gwidth[g]);
 	}
 
 	int nacc = 0;
@@ -215,8 +294,11 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 			T.nf = A->nfactors;
 		for (int f = 0; f < T.nf; f++)
 		{
-			Table::Col *c = scan->find(A->col[f] ? A->col[f]
-						   : "");
+			Table *at = nullptr;
+
+			GG_TRY(resolve_src(d, scan, A->src[f], d->njoins,
+					   "agg src of aggregate", a, &at));
+			Table::Col *c = at->find(A->col[f] ? A->col[f] : "");
 
 			if (!c)
 				return fail(GG_EINVAL,
@@ -228,7 +310,8 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 			T.nulls[f] = (const uint8_t *) c->nulls;
 			T.width[f] = coltype_width(c->type);
 			T.mod[f] = A->mod[f];
-			R->pred_bytes_per_row += T.width[f];
+			R->pred_bytes_per_row += col_bytes(c->dev, A->src[f],
+							   T.width[f]);
 		}
 
 		/* lower onto accumulator slots; helper slots re-read the
@@ -240,6 +323,8 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 				return -1;
 			R->dev.aggs[nacc] = T;
 			R->dev.aggs[nacc].kind = devkind;
+			for (int f = 0; f < T.nf; f++)
+				R->dev.pl.asrc[nacc][f] = A->src[f];
 			return nacc++;
 		};
 		PlanResolved::OutAgg O{A->kind, -1, -1};
@@ -255,8 +340,11 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 				const PlanAggDev &H = R->dev.aggs[h];
 				bool same = H.nf == T.nf;
 
+				/* same columns read at the same rows: a
+				 * table joined twice is two sources */
 				for (int f = 0; same && f < T.nf; f++)
-					same = H.col[f] == T.col[f];
+					same = H.col[f] == T.col[f] &&
+						R->dev.pl.asrc[h][f] == A->src[f];
 				if (same)
 					O.cnt = h;
 			}
@@ -299,14 +387,14 @@ static uint64_t next_pow2_pl(uint64_t v)
 static constexpr uint64_t PL_NSLOTS = 1ull << 18;
 static constexpr unsigned long long PL_EMPTY_HOST = 0x8000000000000000ull;
 
-/* empty the group table, zero the accumulators and the error word */
+/* empty the group table and zero the accumulators; the error word is
+ * exec_plan's, which clears it ahead of the join builds */
 static gg_status
 plan_reset_table(hipStream_t s, const PlanDev &D)
 {
 	GG_HIP(launch_fill_u64(s, D.tkeys, D.nslots, PL_EMPTY_HOST));
 	GG_HIP(hipMemsetAsync(D.tvals, 0, D.nslots * (size_t) D.naggs * 16,
 			      s));
-	GG_HIP(hipMemsetAsync(D.err, 0, 8, s));
 	return GG_OK;
 }
 
@@ -352,8 +440,9 @@ plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
  * 4x margin (long double keeps int64 exact; the
  * margin absorbs product rounding). */
 static bool
-plan_fast_tier_provable(Engine &e, const PlanDev &D)
+plan_fast_tier_provable(Engine &e, const PlanResolved *R)
 {
+	const PlanDev &D = R->dev;
 	long double rows_pb = (long double) D.n /
 		(long double) pl_grid(D.n) + 256.0L;
 
@@ -373,7 +462,11 @@ plan_fast_tier_provable(Engine &e, const PlanDev &D)
 		{
 			long long mn, mx;
 
-			if (engine_col_minmax(e, A.col[f], A.width[f], D.n,
+			/* over the factor's OWN table: a payload column
+			 * is bounded by the min/max of the whole build
+			 * column (loose but valid), and is only that long */
+			if (engine_col_minmax(e, A.col[f], A.width[f],
+					      R->src_rows[D.pl.asrc[a][f]],
 					      &mn, &mx) != GG_OK)
 				return false;
 			long double a0 = (long double) mn;
@@ -432,12 +525,25 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	if (!ctr)
 		return fail(GG_ENOMEM, "plan scratch");
 
-	/* 1. build the semi-join structures (sizing guard as in the
-	 * named pipelines: dense bitmap iff max(key) <= 8x rows) */
+	/* the kernels' error word: the INNER builds report duplicate keys
+	 * in it, so it is cleared ahead of them, not just before the scan */
+	unsigned long long *derr = (unsigned long long *)
+		p->sget("plan.err", 8);
+
+	if (!derr)
+		return fail(GG_ENOMEM, "plan scratch");
+	R->dev.err = derr;
+	GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
+
+	/* 1. build the join structures (sizing guard as in the named
+	 * pipelines: dense iff max(key) <= 8x rows).  SEMI: membership
+	 * bitmap / hash set.  INNER: key -> build-row-index map, dense
+	 * uint32 array or a row-index array parallel to the hash keys */
 	for (size_t j = 0; j < R->joins.size(); j++)
 	{
 		PlanResolved::BJoin &B = R->joins[j];
-		char nm[32];
+		const bool inner = B.bd.kind == GG_JOIN_INNER;
+		char nm[32], nmi[32];
 		Timed tm(e.stream);
 
 		if (B.bd.kw == 8 && !B.dlen && !B.hslots)
@@ -454,7 +560,26 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		if (!B.dlen && !B.hslots)
 			B.hslots = next_pow2_pl(2 * (uint64_t) B.bd.n + 2);
 		std::snprintf(nm, sizeof(nm), "plan.j%zu", j);
-		if (B.dlen)
+		std::snprintf(nmi, sizeof(nmi), "plan.j%zu.idx", j);
+		B.bd.err = derr;
+		B.bd.idx = nullptr;
+		if (B.dlen && inner)
+		{
+			uint32_t *idx = (uint32_t *)
+				p->sget(nmi, (size_t) B.dlen * 4);
+
+			if (!idx)
+				return fail(GG_ENOMEM, "plan join index");
+			/* every entry PL_NOROW = absent */
+			GG_HIP(hipMemsetAsync(idx, 0xFF, (size_t) B.dlen * 4,
+					      e.stream));
+			B.bd.idx = idx;
+			B.bd.bits = nullptr;
+			B.bd.dlen = B.dlen;
+			B.bd.hkeys = nullptr;
+			B.bd.hslots = 0;
+		}
+		else if (B.dlen)
 		{
 			size_t words = (size_t) (B.dlen / 64 + 2);
 			unsigned long long *bits = (unsigned long long *)
@@ -480,6 +605,16 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			B.bd.dlen = 0;
 			B.bd.hkeys = hk;
 			B.bd.hslots = B.hslots;
+			if (inner)
+			{
+				/* read only where a key was installed, so
+				 * it needs no initial value */
+				B.bd.idx = (uint32_t *)
+					p->sget(nmi, B.hslots * 4);
+				if (!B.bd.idx)
+					return fail(GG_ENOMEM,
+						    "plan join index");
+			}
 		}
 		GG_HIP(launch_plan_build(e.stream, B.bd));
 		{
@@ -494,8 +629,11 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		R->dev.joins[j].dlen = B.bd.dlen;
 		R->dev.joins[j].hkeys = B.bd.hkeys;
 		R->dev.joins[j].hslots = B.bd.hslots;
-		p->stat(B.dlen ? "path_plan_join_bitmap"
-			: "path_plan_join_hash").launches++;
+		R->dev.pl.jidx[j] = B.bd.idx;
+		p->stat(inner ? (B.dlen ? "path_plan_join_index_dense"
+				 : "path_plan_join_index_hash")
+			: (B.dlen ? "path_plan_join_bitmap"
+			   : "path_plan_join_hash")).launches++;
 	}
 
 	/* 2. group table + fused scan, 3. compact */
@@ -508,20 +646,17 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		p->sget("plan.tkeys", nslots * 8);
 	unsigned long long *tvals = (unsigned long long *)
 		p->sget("plan.tvals", nslots * (size_t) naggs * 16);
-	unsigned long long *derr = (unsigned long long *)
-		p->sget("plan.err", 8);
 	unsigned long long *dout = (unsigned long long *)
 		p->sget("plan.out", cap * (size_t) rowsz * 8);
 	unsigned long long ng = 0, herr = 0;
 
-	if (!tkeys || !tvals || !derr)
+	if (!tkeys || !tvals)
 		return fail(GG_ENOMEM, "plan group table");
 	if (!dout)
 		return fail(GG_ENOMEM, "plan out");
 	R->dev.tkeys = tkeys;
 	R->dev.tvals = tvals;
 	R->dev.nslots = nslots;
-	R->dev.err = derr;
 	{
 		Timed tm(e.stream);
 
@@ -542,7 +677,13 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 					 R->rtc_baked ? R->rtc_baked : R->rtc,
 					 &tm, dout, ctr, &herr));
 	}
-	if (herr == 2ull && R->rtc_baked)
+	if (herr & PL_ERR_DUP_KEY)
+		return fail(GG_ENOTSUP,
+			    "plan: INNER join build key is not unique among "
+			    "the build rows that pass (or is INT64_MIN): "
+			    "row-multiplying joins are not implemented "
+			    "(fall back to standard_ExecutorRun)");
+	if (herr == PL_ERR_BAKE_MISS && R->rtc_baked)
 	{
 		/* the baked kernel saw a group code outside its baked
 		 * set (impossible over immutable tables; defensive) —
@@ -550,6 +691,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		 * generic kernel */
 		R->rtc_baked.reset();
 		p->stat("path_plan_bake_miss").launches++;
+		GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
 		GG_TRY(plan_reset_table(e.stream, R->dev));
 		GG_TRY(plan_scan_compact(e, p, R, R->rtc, nullptr, dout, ctr,
 					 &herr));
@@ -772,7 +914,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			for (size_t i = 0; i < ng; i++)
 				codes[i] = (long long) rows[i * rowsz];
 
-			bool fastok = plan_fast_tier_provable(e, R->dev);
+			bool fastok = plan_fast_tier_provable(e, R);
 			gg_status rs = plan_rtc_compile(
 				R->dev, R->dev.gnulls[0] != nullptr,
 				R->dev.gnulls[1] != nullptr, &R->rtc_baked,

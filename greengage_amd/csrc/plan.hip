@@ -8,6 +8,10 @@
  *                 range quals; NULL input → qual not true)
  *   semi joins    nodeHash.c:88 (build) / nodeHashjoin.c:78 (probe);
  *                 NULL join keys never match (nodeHash.c:1070–1077)
+ *   inner joins   unique-keyed build side (PK–FK): the build maps key ->
+ *                 build-row index, the scan gathers payload columns
+ *                 (group keys, factors, chained probe keys) through it
+ *                 (nodeHashjoin.c HJ_NEED_NEW_OUTER -> HJ_SCAN_BUCKET)
  *   group-by      execHHashagg.c:905 find-or-create; NULL keys group
  *                 together (:531)
  *   transitions   nodeAgg.c:413–460 strict rules: SUM/COUNT(col) skip
@@ -122,8 +126,14 @@ pl_preds_pass4(const PlanPredDev *preds, int npreds, int64_t i, int64_t S,
 	}
 }
 
-/* ---- semi-join build ------------------------------------------------ */
+/* ---- join build ------------------------------------------------------
+ * INNER = 0: today's membership set (bitmap or hash set), duplicates
+ * welcome.  INNER = 1: key -> build-row-index map for a unique-keyed
+ * build side; a second passing row with the same non-NULL key sets
+ * PL_ERR_DUP_KEY and the execute is refused.  The probe runs in a later
+ * kernel, so the index write needs no ordering against the key CAS. */
 
+template <int INNER>
 __global__ __launch_bounds__(PL_THREADS, 4)
 void k_plan_build(PlanBuildDev B)
 {
@@ -139,7 +149,21 @@ void k_plan_build(PlanBuildDev B)
 		{
 			int64_t k = pl_ld<0>(B.key, B.kw, i);
 
-			if (B.bits)
+			if (INNER && B.dlen)
+			{
+				/* dense map: first row to claim the entry
+				 * wins, a later one is a duplicate.  The
+				 * sizing guard keeps every key inside the map
+				 * (dlen = max + 1, and a negative key anywhere
+				 * in the column forces the hash path); a key
+				 * outside it would lose its partners, so it
+				 * refuses the execute instead */
+				if (k < 0 || k >= B.dlen ||
+				    atomicCAS(&B.idx[k], PL_NOROW,
+					      (uint32_t) i) != PL_NOROW)
+					atomicOr(B.err, PL_ERR_DUP_KEY);
+			}
+			else if (B.bits)
 			{
 				if (k >= 0 && k < B.dlen)
 					atomicOr(&B.bits[k >> 6],
@@ -152,19 +176,36 @@ void k_plan_build(PlanBuildDev B)
 				uint64_t pos = (uint64_t) gg_hashint8(k) &
 					(B.hslots - 1);
 
+				if (INNER && t == 0)
+				{
+					/* INT64_MIN encodes as the empty
+					 * sentinel and could never be found */
+					atomicOr(B.err, PL_ERR_DUP_KEY);
+					continue;
+				}
 				for (uint64_t it = 0; it < B.hslots; it++)
 				{
 					unsigned long long cur =
 						B.hkeys[pos];
 
 					if (cur == t)
+					{
+						if (INNER)
+							atomicOr(B.err,
+								 PL_ERR_DUP_KEY);
 						break;
+					}
 					if (cur == 0)
 					{
 						unsigned long long prev =
 							atomicCAS(&B.hkeys[pos],
 								  0ull, t);
 
+						if (INNER && prev == 0)
+							B.idx[pos] = (uint32_t) i;
+						if (INNER && prev == t)
+							atomicOr(B.err,
+								 PL_ERR_DUP_KEY);
 						if (prev == 0 || prev == t)
 							break;
 						continue;
@@ -178,8 +219,12 @@ void k_plan_build(PlanBuildDev B)
 
 hipError_t launch_plan_build(hipStream_t s, const PlanBuildDev &b)
 {
-	hipLaunchKernelGGL(k_plan_build, dim3(pl_grid(b.n)),
-			   dim3(PL_THREADS), 0, s, b);
+	if (b.kind == GG_JOIN_INNER)
+		hipLaunchKernelGGL(k_plan_build<1>, dim3(pl_grid(b.n)),
+				   dim3(PL_THREADS), 0, s, b);
+	else
+		hipLaunchKernelGGL(k_plan_build<0>, dim3(pl_grid(b.n)),
+				   dim3(PL_THREADS), 0, s, b);
 	return hipGetLastError();
 }
 
@@ -233,35 +278,162 @@ pl_joins_pass(const PlanJoinDev *joins, int njoins, int64_t i)
 	return true;
 }
 
+/* PL = the plan holds an INNER join: the row then carries the build-row
+ * index of every INNER join, and a load of a column whose source is
+ * 1+j indexes with join j's.  Plans without one instantiate PL = 0 and
+ * compile to the code they always had (same treatment as MM below). */
+template <int PL>
+struct PlRow
+{
+};
+
+template <>
+struct PlRow<1>
+{
+	uint32_t r[GG_PLAN_MAX_JOINS];
+};
+
+static_assert(GG_PLAN_MAX_JOINS == 2, "pl_ix selects between two joins");
+
+template <int PL>
+__device__ static inline int64_t
+pl_ix(const PlRow<PL> &R, int src, int64_t i)
+{
+	if constexpr (PL)
+		return src == 0 ? i : (int64_t) (src == 1 ? R.r[0] : R.r[1]);
+	else
+		return i;
+}
+
+/* the same walk for a plan with an INNER join: joins run in descriptor
+ * order, an INNER join leaves its build-row index in R, and a probe key
+ * may itself come from an earlier INNER join's build row */
+__device__ static inline bool
+pl_joins_index(const PlanDev &P, int64_t i, PlRow<1> &R)
+{
+	const PlanJoinDev *joins = P.joins;
+	const int njoins = P.njoins;
+
+	R.r[0] = R.r[1] = 0;
+#pragma unroll
+	for (int j = 0; j < GG_PLAN_MAX_JOINS; j++)
+	{
+		if (j >= njoins)
+			break;
+		const PlanJoinDev &J = joins[j];
+		const bool inner = P.pl.jkind[j] == GG_JOIN_INNER;
+		int64_t pi = pl_ix<1>(R, P.pl.jpsrc[j], i);
+
+		if (J.pnulls && J.pnulls[pi])
+			return false;	/* NULL probe key never matches */
+		int64_t k = pl_ld<0>(J.pkey, J.width, pi);
+
+		if (inner && J.dlen)
+		{
+			/* range check BEFORE the map is touched */
+			if (k < 0 || k >= J.dlen)
+				return false;
+			uint32_t x = P.pl.jidx[j][k];
+
+			if (x == PL_NOROW)
+				return false;
+			R.r[j] = x;
+		}
+		else if (inner)
+		{
+			unsigned long long t = (unsigned long long) k
+				^ 0x8000000000000000ull;
+			uint64_t pos = (uint64_t) gg_hashint8(k) &
+				(J.hslots - 1);
+
+			/* empty BEFORE match: a probe key of INT64_MIN
+			 * encodes as the empty sentinel and must not "hit"
+			 * a slot whose index was never written */
+			for (;;)
+			{
+				unsigned long long cur = J.hkeys[pos];
+
+				if (cur == 0)
+					return false;
+				if (cur == t)
+					break;
+				pos = (pos + 1) & (J.hslots - 1);
+			}
+			R.r[j] = P.pl.jidx[j][pos];
+		}
+		else if (J.bits)
+		{
+			if (k < 0 || k >= J.dlen ||
+			    !((J.bits[k >> 6] >> (k & 63)) & 1))
+				return false;
+		}
+		else
+		{
+			/* SEMI hash set, probed as pl_joins_pass does */
+			unsigned long long t = (unsigned long long) k
+				^ 0x8000000000000000ull;
+			uint64_t pos = (uint64_t) gg_hashint8(k) &
+				(J.hslots - 1);
+
+			for (;;)
+			{
+				unsigned long long cur = J.hkeys[pos];
+
+				if (cur == t)
+					break;
+				if (cur == 0)
+					return false;
+				pos = (pos + 1) & (J.hslots - 1);
+			}
+		}
+	}
+	return true;
+}
+
+template <int PL>
+__device__ static inline bool
+pl_row_joins(const PlanDev &P, int64_t i, PlRow<PL> &R)
+{
+	if constexpr (PL)
+		return pl_joins_index(P, i, R);
+	else
+		return pl_joins_pass(P.joins, P.njoins, i);
+}
+
 /* group code; INT64_MIN bit pattern = empty sentinel (never a code) */
+template <int PL>
 __device__ static inline long long
-pl_group_code(const PlanDev &P, int64_t i)
+pl_group_code(const PlanDev &P, int64_t i, const PlRow<PL> &R)
 {
 	if (P.ngroup == 0)
 		return 0;
+	const int64_t i0 = pl_ix<PL>(R, P.pl.gsrc[0], i);
+
 	if (P.ngroup == 2)
 	{
 		/* two char1 columns; NULL encodes as 256 so NULL groups
 		 * stay distinct per column (execHHashagg.c:531) */
-		long long e0 = (P.gnulls[0] && P.gnulls[0][i]) ? 256
-			: pl_ld<0>(P.gcol[0], P.gwidth[0], i);
-		long long e1 = (P.gnulls[1] && P.gnulls[1][i]) ? 256
-			: pl_ld<0>(P.gcol[1], P.gwidth[1], i);
+		const int64_t i1 = pl_ix<PL>(R, P.pl.gsrc[1], i);
+		long long e0 = (P.gnulls[0] && P.gnulls[0][i0]) ? 256
+			: pl_ld<0>(P.gcol[0], P.gwidth[0], i0);
+		long long e1 = (P.gnulls[1] && P.gnulls[1][i1]) ? 256
+			: pl_ld<0>(P.gcol[1], P.gwidth[1], i1);
 
 		return e0 * 512 + e1;
 	}
-	if (P.gnulls[0] && P.gnulls[0][i])
+	if (P.gnulls[0] && P.gnulls[0][i0])
 		return GG_PLAN_NULL_KEY;
-	return pl_ld<0>(P.gcol[0], P.gwidth[0], i);
+	return pl_ld<0>(P.gcol[0], P.gwidth[0], i0);
 }
 
 /* strict-transition aggregate input (nodeAgg.c:413).  MM = the plan
  * holds a MIN/MAX word: plans without one instantiate the kernel with
  * MM = 0 and carry none of the kind >= 3 branches (the interpreted
  * Q1-shaped plan measured 2.6% slower with them in the row loop). */
-template <int MM>
+template <int MM, int PL>
 __device__ static inline bool
-pl_agg_val(const PlanAggDev &a, int64_t i, __int128 *out)
+pl_agg_val(const PlanAggDev &a, const int8_t *src, int64_t i,
+	   const PlRow<PL> &R, __int128 *out)
 {
 	if (a.kind == 0)	/* COUNT(*) */
 	{
@@ -269,7 +441,7 @@ pl_agg_val(const PlanAggDev &a, int64_t i, __int128 *out)
 		return true;
 	}
 	for (int f = 0; f < a.nf; f++)
-		if (a.nulls[f] && a.nulls[f][i])
+		if (a.nulls[f] && a.nulls[f][pl_ix<PL>(R, src[f], i)])
 			return false;	/* strict: skip NULL input */
 	if (a.kind == 1)	/* COUNT(col) */
 	{
@@ -281,7 +453,8 @@ pl_agg_val(const PlanAggDev &a, int64_t i, __int128 *out)
 
 		for (int f = 0; f < a.nf; f++)
 		{
-			int64_t x = pl_ld<0>(a.col[f], a.width[f], i);
+			int64_t x = pl_ld<0>(a.col[f], a.width[f],
+					     pl_ix<PL>(R, src[f], i));
 
 			if (a.mod[f] == 1)
 				x = 100 - x;
@@ -361,15 +534,15 @@ pl_atomic_add128(unsigned long long *w, unsigned long long vlo,
  * accumulator acc(a).  ATOMIC = the accumulators live in LDS
  * or global memory, else in registers.  Exact 128-bit add, or unsigned
  * max of the encoded MIN/MAX word. */
-template <int MM, bool ATOMIC, class Acc>
+template <int MM, int PL, bool ATOMIC, class Acc>
 __device__ static inline void
-pl_row_aggs(const PlanDev &P, int64_t i, Acc acc)
+pl_row_aggs(const PlanDev &P, int64_t i, const PlRow<PL> &R, Acc acc)
 {
 	for (int a = 0; a < P.naggs; a++)
 	{
 		__int128 v;
 
-		if (!pl_agg_val<MM>(P.aggs[a], i, &v))
+		if (!pl_agg_val<MM, PL>(P.aggs[a], P.pl.asrc[a], i, R, &v))
 			continue;
 		unsigned long long vlo = (unsigned long long) v;
 		unsigned long long vhi = (unsigned long long) (v >> 64);
@@ -412,7 +585,7 @@ pl_fold_flush(int kind, unsigned long long *dst, Rep rep)
 		pl_atomic_add128(dst, lo, hi);
 }
 
-template <int NT, int MM>
+template <int NT, int MM, int PL>
 __global__ __launch_bounds__(PL_THREADS, 4)
 void k_plan_scan_agg(PlanDev P)
 {
@@ -432,10 +605,12 @@ void k_plan_scan_agg(PlanDev P)
 		unsigned long long acc[GG_PLAN_MAX_AGGS][2] = {};
 		auto row = [&](int64_t i)
 		{
-			if (!pl_joins_pass(P.joins, P.njoins, i))
+			PlRow<PL> R;
+
+			if (!pl_row_joins<PL>(P, i, R))
 				return;
-			pl_row_aggs<MM, false>(P, i,
-					       [&](int a) { return acc[a]; });
+			pl_row_aggs<MM, PL, false>(P, i, R,
+						   [&](int a) { return acc[a]; });
 		};
 		int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 
@@ -510,9 +685,11 @@ void k_plan_scan_agg(PlanDev P)
 
 	auto row = [&](int64_t i)
 	{
-		if (!pl_joins_pass(P.joins, P.njoins, i))
+		PlRow<PL> R;
+
+		if (!pl_row_joins<PL>(P, i, R))
 			return;
-		long long code = pl_group_code(P, i);
+		long long code = pl_group_code<PL>(P, i, R);
 		int ls = -1;
 		uint32_t pos = (uint32_t) gg_hashint8(code) & (LSLOTS - 1);
 
@@ -543,7 +720,7 @@ void k_plan_scan_agg(PlanDev P)
 		}
 		if (ls >= 0)
 		{
-			pl_row_aggs<MM, true>(P, i, [&](int a)
+			pl_row_aggs<MM, PL, true>(P, i, R, [&](int a)
 			{
 				return &lvals[lrep][ls][2 * a];
 			});
@@ -554,10 +731,10 @@ void k_plan_scan_agg(PlanDev P)
 
 		if (slot < 0)
 		{
-			atomicOr(P.err, 1ull);
+			atomicOr(P.err, PL_ERR_FULL);
 			return;
 		}
-		pl_row_aggs<MM, true>(P, i, [&](int a)
+		pl_row_aggs<MM, PL, true>(P, i, R, [&](int a)
 		{
 			return &P.tvals[(slot * P.naggs + a) * 2];
 		});
@@ -587,7 +764,7 @@ void k_plan_scan_agg(PlanDev P)
 
 		if (slot < 0)
 		{
-			atomicOr(P.err, 1ull);
+			atomicOr(P.err, PL_ERR_FULL);
 			continue;
 		}
 		for (int a = 0; a < P.naggs; a++)
@@ -607,18 +784,26 @@ hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
 	for (int a = 0; a < p.naggs; a++)
 		if (p.aggs[a].kind >= 3)
 			mm = true;
-	if (ntl && mm)
-		hipLaunchKernelGGL((k_plan_scan_agg<1, 1>), dim3(pl_grid(p.n)),
-				   dim3(PL_THREADS), 0, s, p);
-	else if (ntl)
-		hipLaunchKernelGGL((k_plan_scan_agg<1, 0>), dim3(pl_grid(p.n)),
-				   dim3(PL_THREADS), 0, s, p);
-	else if (mm)
-		hipLaunchKernelGGL((k_plan_scan_agg<0, 1>), dim3(pl_grid(p.n)),
-				   dim3(PL_THREADS), 0, s, p);
-	else
-		hipLaunchKernelGGL((k_plan_scan_agg<0, 0>), dim3(pl_grid(p.n)),
-				   dim3(PL_THREADS), 0, s, p);
+	bool pl = false;
+
+	for (int j = 0; j < p.njoins; j++)
+		if (p.pl.jkind[j] == GG_JOIN_INNER)
+			pl = true;
+#define PL_LAUNCH(NT, MM, PL) \
+	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL>), \
+			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p)
+	switch ((ntl ? 4 : 0) | (mm ? 2 : 0) | (pl ? 1 : 0))
+	{
+		case 0: PL_LAUNCH(0, 0, 0); break;
+		case 1: PL_LAUNCH(0, 0, 1); break;
+		case 2: PL_LAUNCH(0, 1, 0); break;
+		case 3: PL_LAUNCH(0, 1, 1); break;
+		case 4: PL_LAUNCH(1, 0, 0); break;
+		case 5: PL_LAUNCH(1, 0, 1); break;
+		case 6: PL_LAUNCH(1, 1, 0); break;
+		default: PL_LAUNCH(1, 1, 1); break;
+	}
+#undef PL_LAUNCH
 	return hipGetLastError();
 }
 

@@ -82,6 +82,15 @@ struct PlanAggDev
 	int8_t mod[3];
 };
 
+struct PlanPayloadDev
+{
+	const uint32_t *jidx[2];
+	int8_t jkind[2];
+	int8_t jpsrc[2];
+	int8_t gsrc[2];
+	int8_t asrc[8][3];
+};
+
 struct PlanDev
 {
 	int64_t n;
@@ -96,6 +105,7 @@ struct PlanDev
 	uint64_t nslots;
 	unsigned long long *err;
 	PlanAggDev aggs[8];
+	PlanPayloadDev pl;
 };
 
 /* reference hashint8 (hashfunc.c:52 -> hash_any 32-bit path) */
@@ -286,7 +296,16 @@ struct Gen
 	int nbake;
 	bool fast;		/* baked one-word tier */
 	bool nt;		/* nontemporal scan loads */
+	bool payload;		/* the plan holds an INNER join: rows carry
+				 * the build-row indices r0, r1 */
 };
+
+/* the row index a column of source `src` is loaded at: the driving row,
+ * or the build row INNER join src-1 found for it */
+static std::string ix_of(int src)
+{
+	return src ? fmt("r%d", src - 1) : std::string("i");
+}
 
 /* layout guards, tunables and the device helpers */
 static void emit_prelude(std::string &s, const Gen &G)
@@ -308,6 +327,13 @@ static void emit_prelude(std::string &s, const Gen &G)
 		 "static_assert(__builtin_offsetof(PlanDev, aggs) == %zu, \"layout\");\n",
 		 offsetof(PlanDev, joins), offsetof(PlanDev, tkeys),
 		 offsetof(PlanDev, err), offsetof(PlanDev, aggs));
+	s += fmt("static_assert(sizeof(PlanPayloadDev) == %zu, \"layout\");\n"
+		 "static_assert(__builtin_offsetof(PlanDev, pl) == %zu, \"layout\");\n"
+		 "static_assert(__builtin_offsetof(PlanPayloadDev, jkind) == %zu, \"layout\");\n"
+		 "static_assert(__builtin_offsetof(PlanPayloadDev, asrc) == %zu, \"layout\");\n",
+		 sizeof(PlanPayloadDev), offsetof(PlanDev, pl),
+		 offsetof(PlanPayloadDev, jkind),
+		 offsetof(PlanPayloadDev, asrc));
 
 	/* baked variant: more replicas by default — the accumulator
 	 * array has only nbake slots, so per-word contention is higher
@@ -362,7 +388,10 @@ static void emit_row_pass(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
 
-	s += "\tauto row_pass = [&](int64_t i) -> bool\n\t{\n";
+	s += G.payload
+		? "\tauto row_pass = [&](int64_t i, uint32_t &r0, uint32_t &r1)"
+		  " -> bool\n\t{\n"
+		: "\tauto row_pass = [&](int64_t i) -> bool\n\t{\n";
 	for (int p = 0; p < D.npreds; p++)
 	{
 		emit_ld(s, fmt("v%d", p).c_str(),
@@ -376,13 +405,40 @@ static void emit_row_pass(std::string &s, const Gen &G)
 	}
 	for (int j = 0; j < D.njoins; j++)
 	{
+		std::string pi = ix_of(D.pl.jpsrc[j]);
+
 		if (D.joins[j].pnulls)
-			s += fmt("\t\tif (P.joins[%d].pnulls[i]) return false;\n",
-				 j);
+			s += fmt("\t\tif (P.joins[%d].pnulls[%s]) return false;\n",
+				 j, pi.c_str());
+		/* a gathered probe key (chained join) is never streamed */
 		emit_ld(s, fmt("k%d", j).c_str(),
 			fmt("P.joins[%d].pkey", j).c_str(), D.joins[j].width,
-			"i");
-		if (D.joins[j].bits)
+			pi.c_str());
+		if (D.pl.jkind[j] == GG_JOIN_INNER && D.joins[j].dlen)
+			/* dense index map: range check before the map is
+			 * touched, 0xFFFFFFFF = no build row */
+			s += fmt("\t\tif (k%d < 0 || k%d >= P.joins[%d].dlen)\n"
+				 "\t\t\treturn false;\n"
+				 "\t\tr%d = P.pl.jidx[%d][k%d];\n"
+				 "\t\tif (r%d == 0xFFFFFFFFu) return false;\n",
+				 j, j, j, j, j, j, j);
+		else if (D.pl.jkind[j] == GG_JOIN_INNER)
+			/* key -> index hash map; EMPTY is tested BEFORE the
+			 * match so a probe key of INT64_MIN (encoded 0 = the
+			 * empty sentinel) finds nothing and never reads an
+			 * unwritten index */
+			s += fmt("\t\t{\n"
+				 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
+				 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
+				 "\t\t\tfor (;;) {\n"
+				 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
+				 "\t\t\t\tif (cur == 0) return false;\n"
+				 "\t\t\t\tif (cur == t) break;\n"
+				 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
+				 "\t\t\t}\n"
+				 "\t\t\tr%d = P.pl.jidx[%d][pos];\n\t\t}\n",
+				 j, j, j, j, j, j, j);
+		else if (D.joins[j].bits)
 			s += fmt("\t\tif (k%d < 0 || k%d >= P.joins[%d].dlen ||\n"
 				 "\t\t    !((P.joins[%d].bits[k%d >> 6] >> (k%d & 63)) & 1))\n"
 				 "\t\t\treturn false;\n", j, j, j, j, j, j);
@@ -406,23 +462,34 @@ static void emit_row_pass(std::string &s, const Gen &G)
  * prove P.aggs[i].col[f] aliases across aggs, so without this
  * the kernel issued 13 per-row VMEM loads where the
  * hand-written k_q1_agg issues 7 (measured via offline ISA
- * dump, tools/rtc_dump_local.cpp). */
+ * dump, tools/rtc_dump_local.cpp).  A load is one (pointer, width,
+ * source): a table joined twice as INNER is two sources, and its
+ * columns are then read at two different build rows. */
 static void emit_agg_vals(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
-	std::vector<std::pair<const void *, int>> uniq;
+	struct Ld
+	{
+		const void *col;
+		int width, src;
+	};
+	std::vector<Ld> uniq;
 	auto var_of = [&](int a, int f) -> int
 	{
 		const void *c = D.aggs[a].col[f];
 		int w = D.aggs[a].width[f];
+		int src = D.pl.asrc[a][f];
 
 		for (size_t u = 0; u < uniq.size(); u++)
-			if (uniq[u].first == c && uniq[u].second == w)
+			if (uniq[u].col == c && uniq[u].width == w &&
+			    uniq[u].src == src)
 				return (int) u;
-		uniq.push_back({c, w});
+		uniq.push_back({c, w, src});
 		emit_ld(s, fmt("xu%d", (int) uniq.size() - 1).c_str(),
-			fmt("P.aggs[%d].col[%d]", a, f).c_str(), w, "i",
-			G.nt);
+			fmt("P.aggs[%d].col[%d]", a, f).c_str(), w,
+			ix_of(D.pl.asrc[a][f]).c_str(),
+			/* gathered payload loads are never nontemporal */
+			G.nt && !D.pl.asrc[a][f]);
 		return (int) uniq.size() - 1;
 	};
 	/* the factor as it enters a product: the loaded var or its
@@ -436,7 +503,10 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 			: fmt("xu%d", u);
 	};
 
-	s += "\tauto agg_vals = [&](int64_t i, VAT *av, bool *aok)\n\t{\n";
+	s += G.payload
+		? "\tauto agg_vals = [&](int64_t i, uint32_t r0, uint32_t r1, "
+		  "VAT *av, bool *aok)\n\t{\n"
+		: "\tauto agg_vals = [&](int64_t i, VAT *av, bool *aok)\n\t{\n";
 	/* pass 1: one load per distinct (pointer, width) */
 	for (int a = 0; a < D.naggs; a++)
 		if (D.aggs[a].kind >= 2)
@@ -480,8 +550,9 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 		s += fmt("\t\taok[%d] = true;\n", a);
 		for (int f = 0; f < D.aggs[a].nf; f++)
 			if (D.aggs[a].nulls[f])
-				s += fmt("\t\tif (P.aggs[%d].nulls[%d][i]) aok[%d] = false;\n",
-					 a, f, a);
+				s += fmt("\t\tif (P.aggs[%d].nulls[%d][%s]) aok[%d] = false;\n",
+					 a, f, ix_of(D.pl.asrc[a][f]).c_str(),
+					 a);
 		if (D.aggs[a].kind == 1)
 			s += fmt("\t\tav[%d] = 1;\n", a);
 		else if (D.aggs[a].kind >= 3)
@@ -510,27 +581,30 @@ static void emit_loop_head(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
 	static const char *const ld[] = {
-		"(long long) ((const uint8_t *) P.gcol[%d])[i]",
-		"(long long) ((const int32_t *) P.gcol[%d])[i]",
-		"((const int64_t *) P.gcol[%d])[i]"};
+		"(long long) ((const uint8_t *) P.gcol[%d])[%s]",
+		"(long long) ((const int32_t *) P.gcol[%d])[%s]",
+		"((const int64_t *) P.gcol[%d])[%s]"};
+	std::string gi[2] = {ix_of(D.pl.gsrc[0]), ix_of(D.pl.gsrc[1])};
 
 	s += R"GG(
 	for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 	     i < P.n; i += stride)
 	{
-		if (!row_pass(i))
-			continue;
 )GG";
+	s += G.payload
+		? "\t\tuint32_t r0 = 0, r1 = 0;\n\n"
+		  "\t\tif (!row_pass(i, r0, r1))\n\t\t\tcontinue;\n"
+		: "\t\tif (!row_pass(i))\n\t\t\tcontinue;\n";
 	if (D.ngroup == 2)
 	{
 		/* two char1 columns; NULL encodes as 256 */
 		for (int g = 0; g < 2; g++)
 		{
-			std::string e = fmt(ld[0], g);
+			std::string e = fmt(ld[0], g, gi[g].c_str());
 
 			if (G.gnull[g])
-				e = fmt("(P.gnulls[%d][i] ? 256 : %s)", g,
-					e.c_str());
+				e = fmt("(P.gnulls[%d][%s] ? 256 : %s)", g,
+					gi[g].c_str(), e.c_str());
 			s += fmt("\t\tlong long e%d = %s;\n", g, e.c_str());
 		}
 		s += "\t\tlong long code = e0 * 512 + e1;\n";
@@ -538,10 +612,11 @@ static void emit_loop_head(std::string &s, const Gen &G)
 	else if (D.ngroup == 1)
 	{
 		std::string e = fmt(ld[D.gwidth[0] == 1 ? 0
-				       : D.gwidth[0] == 4 ? 1 : 2], 0);
+				       : D.gwidth[0] == 4 ? 1 : 2], 0,
+				    gi[0].c_str());
 
 		if (G.gnull[0])
-			e = "P.gnulls[0][i] ? (long long) "
+			e = "P.gnulls[0][" + gi[0] + "] ? (long long) "
 				"0x8000000000000001ull : (" + e + ")";
 		s += "\t\tlong long code = " + e + ";\n";
 	}
@@ -549,8 +624,9 @@ static void emit_loop_head(std::string &s, const Gen &G)
 		VAT av[NA];
 		bool aok[NA];
 
-		agg_vals(i, av, aok);
 )GG";
+	s += G.payload ? "\t\tagg_vals(i, r0, r1, av, aok);\n"
+		       : "\t\tagg_vals(i, av, aok);\n";
 }
 
 /* where a row's transition lands */
@@ -843,7 +919,12 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	 * +11%.  Default ON for baked kernels; GG_PLAN_RTC_NT=0 reverts. */
 	const char *ntv = getenv("GG_PLAN_RTC_NT");
 	bool nt = nbake > 0 && !(ntv && ntv[0] == '0');
-	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt};
+	bool payload = false;
+
+	for (int j = 0; j < D.njoins; j++)
+		if (D.pl.jkind[j] == GG_JOIN_INNER)
+			payload = true;
+	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt, payload};
 	std::string s;
 
 	emit_prelude(s, G);

@@ -52,12 +52,14 @@ class _PlanScan(ctypes.Structure):
 
 class _PlanJoin(ctypes.Structure):
     _fields_ = [("build", _PlanScan), ("build_key", ctypes.c_char_p),
-                ("probe_key", ctypes.c_char_p)]
+                ("probe_key", ctypes.c_char_p), ("kind", ctypes.c_int),
+                ("probe_src", ctypes.c_int8)]
 
 
 class _PlanAgg(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("nfactors", ctypes.c_int),
-                ("col", ctypes.c_char_p * 3), ("mod", ctypes.c_int8 * 3)]
+                ("col", ctypes.c_char_p * 3), ("mod", ctypes.c_int8 * 3),
+                ("src", ctypes.c_int8 * 3)]
 
 
 class _PlanDesc(ctypes.Structure):
@@ -65,7 +67,7 @@ class _PlanDesc(ctypes.Structure):
                 ("njoins", ctypes.c_int),
                 ("group_cols", ctypes.c_char_p * 2),
                 ("ngroup", ctypes.c_int), ("aggs", _PlanAgg * 8),
-                ("naggs", ctypes.c_int)]
+                ("naggs", ctypes.c_int), ("group_src", ctypes.c_int8 * 2)]
 
 
 NEG_INF = -(1 << 63)          # one-sided range bounds
@@ -74,6 +76,8 @@ PLAN_NULL_KEY = -(1 << 63) + 1
 # gg_plan_aggkind (engine_abi.h)
 AGG_COUNT_STAR, AGG_COUNT_COL, AGG_SUM = 0, 1, 2
 AGG_MIN, AGG_MAX, AGG_AVG = 3, 4, 5
+# gg_plan_joinkind (engine_abi.h)
+JOIN_SEMI, JOIN_INNER = 0, 1
 
 
 class KernelStat(ctypes.Structure):
@@ -138,6 +142,8 @@ def _load():
     lib.gg_engine_comm_init.argtypes = [ctypes.c_void_p]
     lib.gg_engine_compile_plan.argtypes = [ctypes.POINTER(_PlanDesc),
                                            ctypes.POINTER(I32)]
+    lib.gg_engine_plan_desc_size.argtypes = []
+    lib.gg_engine_plan_desc_size.restype = ctypes.c_size_t
     lib.gg_engine_table_set_nulls.argtypes = [I32, ctypes.c_char_p,
                                               ctypes.c_void_p]
     lib.gg_engine_hash_groupby_i64_n.argtypes = [
@@ -393,14 +399,30 @@ class Engine:
 
         preds: [(col, lo, hi)]  (half-open; NEG_INF/POS_INF one-sided)
         joins: [{"table": h, "build_key": c, "probe_key": c,
-                 "preds": [...]}]  (hash SEMI-join filters)
-        group_cols: 0-2 column names of the driving table
+                 "preds": [...], "kind": "semi"|"inner",
+                 "probe_src": k}]
+               "semi" (default) is a filter; "inner" joins a
+               unique-keyed build table whose columns the plan can then
+               read.  probe_src k takes probe_key from the build table
+               of the earlier INNER join k-1 (0 = driving table).
+        group_cols: 0-2 columns
         aggs: ["count"] | ("count", col) |
               ("sum", [(col, "id"|"sub100"|"add100"), ...]) |
               ("min", (col, mod)) | ("max", (col, mod)) |
               ("avg", [(col, mod), ...])
+        A group column or aggregate factor `col` is a column name of
+        the driving table, or a pair (join_index, name) for a column of
+        that INNER join's build table.
         """
         mods = {"id": 0, "sub100": 1, "add100": 2}
+        jkinds = {"semi": JOIN_SEMI, "inner": JOIN_INNER}
+
+        def colref(c):
+            """(name bytes, source): 0 = driving, 1+k = join k"""
+            if isinstance(c, str):
+                return c.encode(), 0
+            k, name = c
+            return name.encode(), 1 + k
 
         def fill_scan(dst, table, plist):
             dst.table = table
@@ -418,9 +440,11 @@ class Engine:
                       list(spec.get("preds", ())))
             d.joins[j].build_key = spec["build_key"].encode()
             d.joins[j].probe_key = spec["probe_key"].encode()
+            d.joins[j].kind = jkinds[spec.get("kind", "semi")]
+            d.joins[j].probe_src = spec.get("probe_src", 0)
         d.ngroup = len(group_cols)
         for g, c in enumerate(group_cols):
-            d.group_cols[g] = c.encode()
+            d.group_cols[g], d.group_src[g] = colref(c)
         d.naggs = len(aggs)
         kinds = []
         for a, spec in enumerate(aggs):
@@ -430,24 +454,24 @@ class Engine:
             elif spec[0] == "count":
                 d.aggs[a].kind = AGG_COUNT_COL
                 d.aggs[a].nfactors = 1
-                d.aggs[a].col[0] = spec[1].encode()
+                d.aggs[a].col[0], d.aggs[a].src[0] = colref(spec[1])
                 d.aggs[a].mod[0] = 0
             elif spec[0] in ("min", "max"):
                 # exactly one factor; a factor LIST is passed through
                 # so the engine's nfactors != 1 rejection is reachable
-                fs = ([spec[1]] if isinstance(spec[1][0], str)
-                      else list(spec[1]))
+                fs = ([spec[1]] if len(spec[1]) == 2 and
+                      isinstance(spec[1][1], str) else list(spec[1]))
                 d.aggs[a].kind = AGG_MIN if spec[0] == "min" else AGG_MAX
                 d.aggs[a].nfactors = len(fs)
                 for f, (c, m) in enumerate(fs):
-                    d.aggs[a].col[f] = c.encode()
+                    d.aggs[a].col[f], d.aggs[a].src[f] = colref(c)
                     d.aggs[a].mod[f] = mods[m]
             else:
                 assert spec[0] in ("sum", "avg"), spec
                 d.aggs[a].kind = AGG_SUM if spec[0] == "sum" else AGG_AVG
                 d.aggs[a].nfactors = len(spec[1])
                 for f, (c, m) in enumerate(spec[1]):
-                    d.aggs[a].col[f] = c.encode()
+                    d.aggs[a].col[f], d.aggs[a].src[f] = colref(c)
                     d.aggs[a].mod[f] = mods[m]
             kinds.append(d.aggs[a].kind)
         h = I32()

@@ -426,9 +426,11 @@ gg_status gg_engine_radix_sort_u64(uint64_t *keys, uint64_t *payload_or_null,
  * The compositional form of the subtree a shim extracts from the
  * PlanState tree (execProcnode.c:925–1148): a driving scan with
  * conjunctive range predicates (ExecQual execQual.c:6260 over the
- * strategy-number operator classes), zero or more hash SEMI-join
- * filters against filtered build tables (nodeHash.c:88 build /
- * nodeHashjoin.c:78 probe, join-qual = key equality), a hash group-by
+ * strategy-number operator classes), zero or more hash joins against
+ * filtered build tables (nodeHash.c:88 build / nodeHashjoin.c:78 probe,
+ * join-qual = key equality): SEMI-join filters, or INNER joins against
+ * a unique-keyed build side whose columns the rest of the plan can
+ * read, a hash group-by
  * over 0–2 key columns (execHHashagg.c:905), and COUNT/SUM/AVG
  * aggregate transitions whose inputs are products of up to three
  * column factors with the (100±col) scaled-decimal modifiers TPC-H
@@ -461,13 +463,53 @@ typedef struct gg_plan_scan
 	int npreds;
 } gg_plan_scan;
 
-/* hash semi-join filter: driving rows survive iff probe_key matches
- * the build_key of some build-side row passing the build preds */
+/* Column sources.  Wherever a descriptor names a column that is read
+ * per driving row (a join's probe_key, a group column, an aggregate
+ * factor) a source byte beside it names the table the column belongs
+ * to: 0 = the driving table (today's meaning, and what a
+ * zero-initialised descriptor says), 1+k = the build table of join k,
+ * which must be a GG_JOIN_INNER join (for a probe_src: one with a lower
+ * index than the probing join).  A source naming a SEMI join, a join
+ * index >= njoins or, for probe_src, a non-earlier join is GG_EINVAL. */
+
+typedef enum gg_plan_joinkind
+{
+	GG_JOIN_SEMI = 0,	/* filter: does the row have a partner? */
+	GG_JOIN_INNER = 1	/* unique-keyed build side with payload */
+} gg_plan_joinkind;
+
+/* hash join against a filtered build table.
+ *
+ * GG_JOIN_SEMI: driving rows survive iff probe_key matches the
+ * build_key of some build-side row passing the build preds.
+ *
+ * GG_JOIN_INNER (nodeHashjoin.c:78–510, HJ_NEED_NEW_OUTER ->
+ * HJ_SCAN_BUCKET): a driving row survives iff its probe key is non-NULL
+ * and equals the build key of a build row that passes the build preds
+ * and has a non-NULL key (NULL keys never match, nodeHash.c:1070); the
+ * row then SEES that build row: columns of the build table can be group
+ * keys, aggregate factors and the probe key of a later join (source
+ * 1+k).  A payload column's NULL flag is read at the build row and
+ * obeys the usual rules: a NULL group key joins the NULL group, a NULL
+ * factor is skipped (strict transition), a NULL chained probe key does
+ * not match.  Joins run in descriptor order.
+ *
+ * Uniqueness: the build key of an INNER join must be unique among the
+ * build rows that pass the build preds and have a non-NULL key (the
+ * PK–FK case); row-multiplying joins are not implemented.  Duplicates
+ * are detected on the device while building and gg_engine_execute then
+ * returns GG_ENOTSUP (the shim falls back) — never a wrong row set.
+ * Duplicates among rows failing the build preds or among NULL-key rows
+ * do not count; SEMI joins accept duplicates.  An INNER build table of
+ * 2^32-1 rows or more is GG_ENOTSUP at compile time (32-bit row
+ * indices), and so is an INNER build key of INT64_MIN at execute. */
 typedef struct gg_plan_join
 {
 	gg_plan_scan build;
 	const char *build_key;
-	const char *probe_key;	/* column of the driving table */
+	const char *probe_key;	/* column of the table probe_src names */
+	int kind;		/* gg_plan_joinkind */
+	int8_t probe_src;	/* source of probe_key (see above) */
 } gg_plan_join;
 
 /* aggregate: COUNT(*) / COUNT(col) (non-NULL, nodeAgg strict rules) /
@@ -505,6 +547,7 @@ typedef struct gg_plan_agg
 	int nfactors;		/* 0 for COUNT(*); 1 for COUNT(col) */
 	const char *col[3];
 	int8_t mod[3];		/* gg_plan_fmod */
+	int8_t src[3];		/* source of col[f] (column sources above) */
 } gg_plan_agg;
 
 typedef struct gg_plan_desc
@@ -521,6 +564,8 @@ typedef struct gg_plan_desc
 	int ngroup;
 	gg_plan_agg aggs[GG_PLAN_MAX_AGGS];
 	int naggs;
+	int8_t group_src[2];	/* source of group_cols[g] (column sources
+				 * above) */
 } gg_plan_desc;
 
 #define GG_PLAN_NULL_KEY (-9223372036854775807LL)	/* INT64_MIN+1 */
@@ -549,6 +594,10 @@ typedef struct gg_plan_desc
  * needs more than GG_PLAN_MAX_AGGS slots returns GG_ENOTSUP; any
  * descriptor with 4 or fewer aggregates compiles. */
 gg_status gg_engine_compile_plan(const gg_plan_desc *desc, gg_pipeline *out);
+
+/* sizeof(gg_plan_desc) as this library was built: lets a binding check
+ * its mirror of the layout without a GPU */
+size_t gg_engine_plan_desc_size(void);
 
 /* Attach a NULL-flag array (1 byte per row, nonzero = NULL) to a
  * registered column — the nullable-scan surface (AO null bitmaps land
