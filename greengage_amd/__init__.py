@@ -13,6 +13,7 @@ from .engine import (  # noqa: F401
     JOIN_SEMI,
     PGDate,
     pgdate,
+    plan_group_bits,
 )
 
 __version__ = "0.1.0"

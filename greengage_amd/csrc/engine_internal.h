@@ -633,6 +633,19 @@ struct PlanPayloadDev
 	int8_t asrc[GG_PLAN_MAX_AGGS][3];	/* source of aggs[a].col[f] */
 };
 
+/* Packed two-column group code (engine_abi.h gg_plan_desc.group_cols):
+ * code = (e0 << shift) | e1, e_g = 0 for NULL, else v - gmin[g] + 1.
+ * Set for every ngroup == 2 plan but the (char1, char1) pair, which
+ * keeps e0 * 512 + e1; filled at the plan's first execute, when the
+ * column ranges are resolved.  Appended after `pl` for the reason given
+ * there: no field of today's plans moves. */
+struct PlanGroupPackDev
+{
+	int packed;
+	int shift;		/* b1, the width of e1 */
+	int64_t gmin[2];
+};
+
 struct PlanDev
 {
 	int64_t n;
@@ -648,6 +661,7 @@ struct PlanDev
 	unsigned long long *err;
 	PlanAggDev aggs[GG_PLAN_MAX_AGGS];
 	PlanPayloadDev pl;
+	PlanGroupPackDev gp;
 };
 
 struct PlanBuildDev

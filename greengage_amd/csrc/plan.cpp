@@ -71,6 +71,11 @@ struct PlanResolved
 	};
 	std::vector<OutAgg> outs;
 	int out_slots = 0;	/* 16-byte arena slots per result row */
+	/* packed pair of group columns (dev.gp.packed): 0 = ranges not yet
+	 * resolved, 1 = resolved and within budget, 2 = over budget; the
+	 * widths are kept for the refusal's message */
+	int gp_state = 0;
+	int gp_bits[2] = {0, 0};
 };
 
 static int coltype_width(gg_coltype t)
@@ -106,6 +111,29 @@ extern "C" size_t
 gg_engine_plan_desc_size(void)
 {
 	return sizeof(gg_plan_desc);
+}
+
+/* widths of a packed two-column group code (engine_abi.h
+ * gg_plan_desc.group_cols).  The span max - min is taken in uint64, where
+ * it cannot overflow; span + 1 values plus the NULL code need
+ * bit_length(span + 1) bits, 65 where span + 1 is 2^64 itself. */
+extern "C" gg_status
+gg_engine_plan_group_bits(const int64_t mn[2], const int64_t mx[2],
+			  int bits[2])
+{
+	for (int g = 0; g < 2; g++)
+	{
+		if (mn[g] > mx[g])	/* no rows */
+		{
+			bits[g] = 1;
+			continue;
+		}
+		uint64_t span = (uint64_t) mx[g] - (uint64_t) mn[g];
+
+		bits[g] = span == UINT64_MAX ? 65
+			: 64 - __builtin_clzll(span + 1);
+	}
+	return bits[0] + bits[1] <= 62 ? GG_OK : GG_ENOTSUP;
 }
 
 /* the table a column source names (engine_abi.h "column sources"):
@@ -261,9 +289,6 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 
 		if (!c)
 			return fail(GG_EINVAL, "plan: group column missing");
-		if (d->ngroup == 2 && c->type != GG_COL_CHAR1)
-			return fail(GG_ENOTSUP,
-				    "plan: 2-column group keys must be char1");
 		R->dev.gcol[g] = c->dev;
 		R->dev.gnulls[g] = (const uint8_t *) c->nulls;
 		R->dev.gwidth[g] = coltype_width(c->type);
@@ -271,6 +296,10 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		R->pred_bytes_per_row += col_bytes(c->dev, d->group_src[g],
 						   R->dev.gwidth[g]);
 	}
+	/* two char1 columns keep the e0 * 512 + e1 code; every other pair
+	 * is packed by the columns' ranges, resolved at the first execute */
+	R->dev.gp.packed = d->ngroup == 2 &&
+		!(R->dev.gwidth[0] == 1 && R->dev.gwidth[1] == 1);
 
 	int nacc = 0;
 	std::vector<int> helpers;	/* helper count slots so far */
@@ -511,6 +540,79 @@ plan_fast_tier_provable(Engine &e, const PlanResolved *R)
 	return true;
 }
 
+/* Packed pair of group columns: resolve the packing parameters at the
+ * plan's first execute, ahead of the hipRTC compile that bakes them.
+ * Each column is ranged over its own whole table (a payload column over
+ * the whole build column: loose but valid, as in the fast-tier proof);
+ * with several segments the ranges are first agreed across them, since
+ * every segment's codes meet in exec_plan's combine and must pack alike.
+ * Widths, acceptance and refusal come from the AGREED ranges only, so
+ * the segments all proceed or all refuse: none may leave on its local
+ * ranges while the others wait in a collective. */
+static gg_status
+plan_group_pack(Engine &e, Pipeline *p, PlanResolved *R)
+{
+	if (R->gp_state == 0)
+	{
+		int nseg = e.cfg.n_segments;
+		/* an empty column is the identity of the fold below */
+		int64_t mn[2] = {INT64_MAX, INT64_MAX};
+		int64_t mx[2] = {INT64_MIN, INT64_MIN};
+
+		for (int g = 0; g < 2; g++)
+		{
+			int64_t rows = R->src_rows[R->dev.pl.gsrc[g]];
+			long long a, b;
+
+			if (rows <= 0)
+				continue;
+			GG_TRY(engine_col_minmax(e, R->dev.gcol[g],
+						 R->dev.gwidth[g], rows, &a, &b));
+			mn[g] = a;
+			mx[g] = b;
+		}
+		if (nseg > 1)
+		{
+			if (!comm_ready())
+				return fail(GG_ESTATE,
+					    "multi-segment plan without comm");
+			unsigned long long *d = (unsigned long long *)
+				p->sget("plan.gprange",
+					(4 + 4 * (size_t) nseg) * 8);
+			int64_t mine[4] = {mn[0], mx[0], mn[1], mx[1]};
+			std::vector<int64_t> all(4 * (size_t) nseg);
+
+			if (!d)
+				return fail(GG_ENOMEM, "plan comm scratch");
+			GG_HIP(hipMemcpy(d, mine, sizeof(mine),
+					 hipMemcpyHostToDevice));
+			GG_TRY(comm_allgather_u64(d, d + 4, 4));
+			GG_HIP(hipMemcpy(all.data(), d + 4, all.size() * 8,
+					 hipMemcpyDeviceToHost));
+			for (int r = 0; r < nseg; r++)
+				for (int g = 0; g < 2; g++)
+				{
+					mn[g] = std::min(mn[g], all[4 * r + 2 * g]);
+					mx[g] = std::max(mx[g],
+							 all[4 * r + 2 * g + 1]);
+				}
+		}
+		R->gp_state = gg_engine_plan_group_bits(mn, mx, R->gp_bits)
+			== GG_OK ? 1 : 2;
+		for (int g = 0; g < 2; g++)
+			R->dev.gp.gmin[g] = mn[g] > mx[g] ? 0 : mn[g];
+		R->dev.gp.shift = R->gp_bits[1];
+	}
+	if (R->gp_state == 2)
+		return fail(GG_ENOTSUP,
+			    "plan: 2-column group key needs %d + %d bits, the "
+			    "packed code holds 62 (fall back to "
+			    "standard_ExecutorRun)", R->gp_bits[0],
+			    R->gp_bits[1]);
+	p->stat("path_plan_group_packed").launches++;
+	return GG_OK;
+}
+
 gg_status
 exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 {
@@ -534,6 +636,8 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		return fail(GG_ENOMEM, "plan scratch");
 	R->dev.err = derr;
 	GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
+	if (R->dev.gp.packed)
+		GG_TRY(plan_group_pack(e, p, R));
 
 	/* 1. build the join structures (sizing guard as in the named
 	 * pipelines: dense iff max(key) <= 8x rows).  SEMI: membership
@@ -815,7 +919,20 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	{
 		long long code = (long long) rows[i * rowsz];
 
-		if (R->dev.ngroup == 2)
+		if (R->dev.gp.packed)
+		{
+			/* (e0 << shift) | e1; e = 0 is NULL, else the
+			 * value's offset from the column minimum, plus 1 */
+			const PlanGroupPackDev &G = R->dev.gp;
+			uint64_t e0 = (uint64_t) code >> G.shift;
+			uint64_t e1 = (uint64_t) code & ((1ull << G.shift) - 1);
+
+			*k0 = e0 ? (int64_t) ((uint64_t) G.gmin[0] + e0 - 1)
+				: GG_PLAN_NULL_KEY;
+			*k1 = e1 ? (int64_t) ((uint64_t) G.gmin[1] + e1 - 1)
+				: GG_PLAN_NULL_KEY;
+		}
+		else if (R->dev.ngroup == 2)
 		{
 			long long e0 = code / 512, e1 = code % 512;
 

@@ -400,8 +400,10 @@ pl_row_joins(const PlanDev &P, int64_t i, PlRow<PL> &R)
 		return pl_joins_pass(P.joins, P.njoins, i);
 }
 
-/* group code; INT64_MIN bit pattern = empty sentinel (never a code) */
-template <int PL>
+/* group code; INT64_MIN bit pattern = empty sentinel (never a code).
+ * GP = the plan groups by a packed pair (PlanGroupPackDev); every other
+ * plan instantiates GP = 0 and compiles to the code it always had. */
+template <int PL, int GP>
 __device__ static inline long long
 pl_group_code(const PlanDev &P, int64_t i, const PlRow<PL> &R)
 {
@@ -409,6 +411,21 @@ pl_group_code(const PlanDev &P, int64_t i, const PlRow<PL> &R)
 		return 0;
 	const int64_t i0 = pl_ix<PL>(R, P.pl.gsrc[0], i);
 
+	if constexpr (GP)
+	{
+		/* e = 0 for NULL, else v - min + 1, in unsigned arithmetic
+		 * (the difference is below 2^62, the operands need not be);
+		 * the widths sum to <= 62, so the code is non-negative */
+		const int64_t i1 = pl_ix<PL>(R, P.pl.gsrc[1], i);
+		unsigned long long e0 = (P.gnulls[0] && P.gnulls[0][i0]) ? 0ull
+			: (unsigned long long) pl_ld<0>(P.gcol[0], P.gwidth[0], i0)
+			- (unsigned long long) P.gp.gmin[0] + 1ull;
+		unsigned long long e1 = (P.gnulls[1] && P.gnulls[1][i1]) ? 0ull
+			: (unsigned long long) pl_ld<0>(P.gcol[1], P.gwidth[1], i1)
+			- (unsigned long long) P.gp.gmin[1] + 1ull;
+
+		return (long long) ((e0 << P.gp.shift) | e1);
+	}
 	if (P.ngroup == 2)
 	{
 		/* two char1 columns; NULL encodes as 256 so NULL groups
@@ -585,7 +602,7 @@ pl_fold_flush(int kind, unsigned long long *dst, Rep rep)
 		pl_atomic_add128(dst, lo, hi);
 }
 
-template <int NT, int MM, int PL>
+template <int NT, int MM, int PL, int GP>
 __global__ __launch_bounds__(PL_THREADS, 4)
 void k_plan_scan_agg(PlanDev P)
 {
@@ -689,7 +706,7 @@ void k_plan_scan_agg(PlanDev P)
 
 		if (!pl_row_joins<PL>(P, i, R))
 			return;
-		long long code = pl_group_code<PL>(P, i, R);
+		long long code = pl_group_code<PL, GP>(P, i, R);
 		int ls = -1;
 		uint32_t pos = (uint32_t) gg_hashint8(code) & (LSLOTS - 1);
 
@@ -789,19 +806,29 @@ hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
 	for (int j = 0; j < p.njoins; j++)
 		if (p.pl.jkind[j] == GG_JOIN_INNER)
 			pl = true;
-#define PL_LAUNCH(NT, MM, PL) \
-	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL>), \
+	/* a packed pair of group columns (PlanGroupPackDev) */
+	const bool gp = p.ngroup == 2 && p.gp.packed;
+#define PL_LAUNCH(NT, MM, PL, GP) \
+	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL, GP>), \
 			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p)
-	switch ((ntl ? 4 : 0) | (mm ? 2 : 0) | (pl ? 1 : 0))
+	switch ((gp ? 8 : 0) | (ntl ? 4 : 0) | (mm ? 2 : 0) | (pl ? 1 : 0))
 	{
-		case 0: PL_LAUNCH(0, 0, 0); break;
-		case 1: PL_LAUNCH(0, 0, 1); break;
-		case 2: PL_LAUNCH(0, 1, 0); break;
-		case 3: PL_LAUNCH(0, 1, 1); break;
-		case 4: PL_LAUNCH(1, 0, 0); break;
-		case 5: PL_LAUNCH(1, 0, 1); break;
-		case 6: PL_LAUNCH(1, 1, 0); break;
-		default: PL_LAUNCH(1, 1, 1); break;
+		case 0: PL_LAUNCH(0, 0, 0, 0); break;
+		case 1: PL_LAUNCH(0, 0, 1, 0); break;
+		case 2: PL_LAUNCH(0, 1, 0, 0); break;
+		case 3: PL_LAUNCH(0, 1, 1, 0); break;
+		case 4: PL_LAUNCH(1, 0, 0, 0); break;
+		case 5: PL_LAUNCH(1, 0, 1, 0); break;
+		case 6: PL_LAUNCH(1, 1, 0, 0); break;
+		case 7: PL_LAUNCH(1, 1, 1, 0); break;
+		case 8: PL_LAUNCH(0, 0, 0, 1); break;
+		case 9: PL_LAUNCH(0, 0, 1, 1); break;
+		case 10: PL_LAUNCH(0, 1, 0, 1); break;
+		case 11: PL_LAUNCH(0, 1, 1, 1); break;
+		case 12: PL_LAUNCH(1, 0, 0, 1); break;
+		case 13: PL_LAUNCH(1, 0, 1, 1); break;
+		case 14: PL_LAUNCH(1, 1, 0, 1); break;
+		default: PL_LAUNCH(1, 1, 1, 1); break;
 	}
 #undef PL_LAUNCH
 	return hipGetLastError();

@@ -44,7 +44,11 @@ struct PlanRtc
 
 /* device-side struct definitions, embedded verbatim so the generated
  * source sees the exact layouts engine_internal.h defines (guarded by
- * a sizeof static_assert) */
+ * a sizeof static_assert).  GP_STRUCT / GP_MEMBER are defined by
+ * emit_prelude: the trailing PlanGroupPackDev block exists only in the
+ * program of a plan with a packed pair of group columns, so every other
+ * plan's kernel keeps the argument block, and with it the binary, it
+ * always had (plan_rtc_launch passes that many bytes) */
 static const char *STRUCT_DEFS = R"GG(
 typedef long long int64_t;
 typedef unsigned long long uint64_t;
@@ -91,6 +95,7 @@ struct PlanPayloadDev
 	int8_t asrc[8][3];
 };
 
+GP_STRUCT
 struct PlanDev
 {
 	int64_t n;
@@ -106,7 +111,7 @@ struct PlanDev
 	unsigned long long *err;
 	PlanAggDev aggs[8];
 	PlanPayloadDev pl;
-};
+GP_MEMBER};
 
 /* reference hashint8 (hashfunc.c:52 -> hash_any 32-bit path) */
 __device__ inline uint32_t gg_hash_uint32(uint32_t k)
@@ -300,6 +305,18 @@ struct Gen
 				 * the build-row indices r0, r1 */
 };
 
+/* a plan with a packed pair of group columns reads PlanDev.gp; every
+ * other plan's program ends PlanDev where it always ended */
+static bool packed_args(const PlanDev &D)
+{
+	return D.ngroup == 2 && D.gp.packed;
+}
+
+static size_t plan_arg_bytes(const PlanDev &D)
+{
+	return packed_args(D) ? sizeof(PlanDev) : offsetof(PlanDev, gp);
+}
+
 /* the row index a column of source `src` is loaded at: the driving row,
  * or the build row INNER join src-1 found for it */
 static std::string ix_of(int src)
@@ -312,6 +329,11 @@ static void emit_prelude(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
 
+	s += packed_args(D)
+		? "#define GP_STRUCT struct PlanGroupPackDev "
+		  "{ int packed; int shift; int64_t gmin[2]; };\n"
+		  "#define GP_MEMBER PlanGroupPackDev gp;\n"
+		: "#define GP_STRUCT\n#define GP_MEMBER\n";
 	s += STRUCT_DEFS;
 	/* the struct text above is a hand copy of engine_internal.h: pin
 	 * every size and the offsets the kernels rely on */
@@ -320,7 +342,7 @@ static void emit_prelude(std::string &s, const Gen &G)
 		 "static_assert(sizeof(PlanAggDev) == %zu, \"layout\");\n"
 		 "static_assert(sizeof(PlanDev) == %zu, \"layout\");\n",
 		 sizeof(PlanPredDev), sizeof(PlanJoinDev), sizeof(PlanAggDev),
-		 sizeof(PlanDev));
+		 plan_arg_bytes(D));
 	s += fmt("static_assert(__builtin_offsetof(PlanDev, joins) == %zu, \"layout\");\n"
 		 "static_assert(__builtin_offsetof(PlanDev, tkeys) == %zu, \"layout\");\n"
 		 "static_assert(__builtin_offsetof(PlanDev, err) == %zu, \"layout\");\n"
@@ -334,6 +356,12 @@ static void emit_prelude(std::string &s, const Gen &G)
 		 sizeof(PlanPayloadDev), offsetof(PlanDev, pl),
 		 offsetof(PlanPayloadDev, jkind),
 		 offsetof(PlanPayloadDev, asrc));
+	if (packed_args(D))
+		s += fmt("static_assert(sizeof(PlanGroupPackDev) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanDev, gp) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanGroupPackDev, gmin) == %zu, \"layout\");\n",
+			 sizeof(PlanGroupPackDev), offsetof(PlanDev, gp),
+			 offsetof(PlanGroupPackDev, gmin));
 
 	/* baked variant: more replicas by default — the accumulator
 	 * array has only nbake slots, so per-word contention is higher
@@ -595,7 +623,30 @@ static void emit_loop_head(std::string &s, const Gen &G)
 		? "\t\tuint32_t r0 = 0, r1 = 0;\n\n"
 		  "\t\tif (!row_pass(i, r0, r1))\n\t\t\tcontinue;\n"
 		: "\t\tif (!row_pass(i))\n\t\t\tcontinue;\n";
-	if (D.ngroup == 2)
+	if (packed_args(D))
+	{
+		/* packed pair (engine_abi.h gg_plan_desc.group_cols): e = 0
+		 * for NULL, else v - min + 1 in unsigned arithmetic; the
+		 * load widths, NULL presence and the shift are baked, the
+		 * minima stay arguments */
+		for (int g = 0; g < 2; g++)
+		{
+			std::string e = fmt(ld[D.gwidth[g] == 1 ? 0
+					       : D.gwidth[g] == 4 ? 1 : 2], g,
+					    gi[g].c_str());
+
+			e = fmt("(unsigned long long) (%s) - (unsigned long long) "
+				"P.gp.gmin[%d] + 1ull", e.c_str(), g);
+			if (G.gnull[g])
+				e = fmt("P.gnulls[%d][%s] ? 0ull : %s", g,
+					gi[g].c_str(), e.c_str());
+			s += fmt("\t\tunsigned long long e%d = %s;\n", g,
+				 e.c_str());
+		}
+		s += fmt("\t\tlong long code = (long long) ((e0 << %d) | e1);\n",
+			 D.gp.shift);
+	}
+	else if (D.ngroup == 2)
 	{
 		/* two char1 columns; NULL encodes as 256 */
 		for (int g = 0; g < 2; g++)
@@ -962,7 +1013,7 @@ plan_rtc_launch(hipStream_t s, const std::shared_ptr<void> &h, PlanDev P,
 		int grid, int block)
 {
 	PlanRtc *rtc = (PlanRtc *) h.get();
-	size_t size = sizeof(P);
+	size_t size = plan_arg_bytes(P);
 	void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &P,
 			  HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
 			  HIP_LAUNCH_PARAM_END};

@@ -144,6 +144,9 @@ def _load():
                                            ctypes.POINTER(I32)]
     lib.gg_engine_plan_desc_size.argtypes = []
     lib.gg_engine_plan_desc_size.restype = ctypes.c_size_t
+    lib.gg_engine_plan_group_bits.argtypes = [
+        ctypes.POINTER(I64), ctypes.POINTER(I64),
+        ctypes.POINTER(ctypes.c_int)]
     lib.gg_engine_table_set_nulls.argtypes = [I32, ctypes.c_char_p,
                                               ctypes.c_void_p]
     lib.gg_engine_hash_groupby_i64_n.argtypes = [
@@ -272,6 +275,18 @@ def _check(rc, what):
 
 def _i128(lo, hi):
     return (hi << 64) | lo
+
+
+def plan_group_bits(mn, mx):
+    """Bit widths of the packed code of a two-column group key whose
+    columns range over [mn[g], mx[g]] (mn[g] > mx[g]: no rows), as
+    gg_engine_plan_group_bits computes them: (status, (b0, b1)).
+    status 0 = the pair fits the 62-bit budget, 5 (GG_ENOTSUP) = it does
+    not.  Host arithmetic only: needs no Engine and no GPU."""
+    bits = (ctypes.c_int * 2)()
+    rc = lib().gg_engine_plan_group_bits((I64 * 2)(*mn), (I64 * 2)(*mx),
+                                         bits)
+    return rc, (bits[0], bits[1])
 
 
 class Engine:
@@ -405,7 +420,13 @@ class Engine:
                unique-keyed build table whose columns the plan can then
                read.  probe_src k takes probe_key from the build table
                of the earlier INNER join k-1 (0 = driving table).
-        group_cols: 0-2 columns
+        group_cols: 0-2 columns of any accepted type (char1, int32,
+               int64) and source.  Two char1 columns keep their fixed
+               code; any other pair is packed into one 64-bit code by
+               the columns' value ranges and must fit 62 bits
+               (plan_group_bits).  The ranges are resolved at the first
+               execute_plan, which raises EngineError status 5 for a
+               pair that does not fit.
         aggs: ["count"] | ("count", col) |
               ("sum", [(col, "id"|"sub100"|"add100"), ...]) |
               ("min", (col, mod)) | ("max", (col, mod)) |

@@ -556,10 +556,34 @@ typedef struct gg_plan_desc
 	gg_plan_join joins[GG_PLAN_MAX_JOINS];
 	int njoins;
 	/* 0 = one global group; 1 = any char1/int32/int64 column;
-	 * 2 = two char1 columns (code = c0*256 + c1).  Group keys of
-	 * INT64_MIN are rejected (open-addressing sentinel); NULL keys
-	 * group together (execHHashagg.c:531), reported as
-	 * GG_PLAN_NULL_KEY. */
+	 * 2 = any two char1/int32/int64 columns, each from any valid source
+	 * (group_src).  NULL keys group together, separately per column
+	 * (execHHashagg.c:531), and are reported as GG_PLAN_NULL_KEY.  Group
+	 * values of INT64_MIN (open-addressing sentinel) or GG_PLAN_NULL_KEY
+	 * are not supported, for one key or two.
+	 *
+	 * Every group travels as ONE 64-bit code through the group table,
+	 * the per-block cache, the baked second stage and the cross-segment
+	 * combine.  Two char1 columns encode e_g = the byte, 256 for NULL,
+	 * code = e0 * 512 + e1.  Every other pair is PACKED by the columns'
+	 * value ranges (columns are immutable):
+	 *   min_g / max_g  signed min/max of the whole column in its own
+	 *                  table, values under NULL flags included; a
+	 *                  payload column is ranged over the whole build
+	 *                  column; with n_segments > 1 the ranges are
+	 *                  agreed across segments (min of mins, max of
+	 *                  maxes, an empty shard being the identity)
+	 *   b_g   = bit_length(max_g - min_g + 1), computed without signed
+	 *           overflow; a column with no rows has b_g = 1
+	 *   e_g   = 0 for a NULL key, else v - min_g + 1: in [0, 2^b_g)
+	 *   code  = (e0 << b1) | e1
+	 * A pair is accepted iff b0 + b1 <= 62 (gg_engine_plan_group_bits):
+	 * the code is then non-negative, below 2^62, and never the empty
+	 * sentinel.  The ranges are resolved at the plan's first execute,
+	 * so an over-budget pair compiles and its first gg_engine_execute
+	 * returns GG_ENOTSUP (every segment alike; the shim falls back).
+	 * The host decodes (key0, key1) before sorting and writing the
+	 * arena.  Either way a two-column plan holds at most 2^18 groups. */
 	const char *group_cols[2];
 	int ngroup;
 	gg_plan_agg aggs[GG_PLAN_MAX_AGGS];
@@ -598,6 +622,15 @@ gg_status gg_engine_compile_plan(const gg_plan_desc *desc, gg_pipeline *out);
 /* sizeof(gg_plan_desc) as this library was built: lets a binding check
  * its mirror of the layout without a GPU */
 size_t gg_engine_plan_desc_size(void);
+
+/* Bit widths of a packed two-column group code (gg_plan_desc.group_cols)
+ * from the two columns' signed value ranges [mn[g], mx[g]]; mn[g] >
+ * mx[g] stands for a column with no rows.  Fills bits[] either way and
+ * returns GG_OK iff bits[0] + bits[1] <= 62, else GG_ENOTSUP.  Pure host
+ * arithmetic: needs neither gg_engine_init nor a GPU, and is what
+ * gg_engine_execute itself decides by. */
+gg_status gg_engine_plan_group_bits(const int64_t mn[2], const int64_t mx[2],
+				    int bits[2]);
 
 /* Attach a NULL-flag array (1 byte per row, nonzero = NULL) to a
  * registered column — the nullable-scan surface (AO null bitmaps land

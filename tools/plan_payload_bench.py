@@ -8,6 +8,11 @@ Descriptors:
           so it must cost what it cost before payload joins existed.
           Measured on the baked, generic (GG_PLAN_BAKE=0) and interpreted
           (GG_PLAN_RTC=0) tiers.
+  q1i32   the same descriptor over a copy of lineitem whose rflag and
+          lstatus are registered as int32 instead of char1: the pair is
+          then no (char1, char1) pair and takes the packed group code
+          (path_plan_group_packed).  Same rows, same groups, same tiers;
+          the two group columns are 4 bytes wide instead of 1.
   year    revenue by order year: lineitem INNER JOIN orders on orderkey
           (dense index map), SUM(price*(100-disc)) and COUNT(*) grouped
           by a payload column.  The year is derived on the host from
@@ -40,7 +45,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--sf", type=int, default=100)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--reps", type=int, default=15)
-ap.add_argument("--only", default="q1,year,nation,q3")
+ap.add_argument("--only", default="q1,q1i32,year,nation,q3")
 ap.add_argument("--tiers", default="baked,generic,interp")
 ap.add_argument("--pkg-root", default=os.path.dirname(
     os.path.dirname(os.path.abspath(__file__))))
@@ -62,7 +67,18 @@ Q1 = ["count", ("sum", [("qty", "id")]), ("sum", [("price", "id")]),
 eng = Engine(device=0, n_segments=1, segment_id=0)
 li = eng.register_synth("lineitem", seed=42, sf=args.sf)
 rows = eng.table_nrows(li)
-od = cu = oy = None
+od = cu = oy = li32 = None
+if "q1i32" in only:
+    import numpy as np
+    li32 = eng.register_table(
+        "lineitem_g32",
+        [(c, ty, eng.fetch_column(li, c, dt).astype(dt2, copy=False))
+         for c, ty, dt, dt2 in (
+             [("shipdate", "int32", np.int32, np.int32)] +
+             [(c, "dec64", np.int64, np.int64)
+              for c in ("qty", "price", "disc", "tax")] +
+             [(c, "int32", np.uint8, np.int32)
+              for c in ("rflag", "lstatus")])], rows)
 if set(only) & {"year", "nation", "q3"}:
     od = eng.register_synth("orders", seed=42, sf=args.sf)
     cu = eng.register_synth("customer", seed=42, sf=args.sf)
@@ -79,9 +95,10 @@ if "year" in only:
 
 
 def compile_desc(name):
-    if name == "q1":
+    if name in ("q1", "q1i32"):
         return eng.compile_plan(
-            li, preds=[("shipdate", NEG_INF, PGDate("1998-08-15") + 1)],
+            li if name == "q1" else li32,
+            preds=[("shipdate", NEG_INF, PGDate("1998-08-15") + 1)],
             group_cols=["rflag", "lstatus"], aggs=Q1)
     if name == "year":
         return eng.compile_plan(

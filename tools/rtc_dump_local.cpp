@@ -21,6 +21,8 @@
  *   join   global-group plan probing one bitmap join and one hash join
  *          with a nullable probe key
  *   pnull  global-group plan with a nullable predicate column
+ *   gp     Q1-shaped plan grouped by a packed (int32, nullable int64)
+ *          pair: generic + baked fast tier
  *   lrepl  q1mmw's 8 two-word aggregates under GG_PLAN_LREPL=32, which
  *          the LDS budget shrinks back to 16 replicas
  *   all    every shape above, DUMPFILE used as a prefix: <prefix><shape>.cu
@@ -216,6 +218,22 @@ dump_shape(const char *shape, const char *file)
 		shape_q6(D, false);
 		D.preds[1].nulls = (const uint8_t *) dummy + 184;
 	}
+	else if (!std::strcmp(shape, "gp"))
+	{
+		static const long long gpcodes[3] = {(1ll << 11) | 1,
+			(7ll << 11) | 0, 2000};
+
+		shape_q1(D, false);
+		D.gwidth[0] = 4;
+		D.gwidth[1] = 8;
+		D.gnulls[1] = (const uint8_t *) dummy + 192;
+		D.gp.packed = 1;
+		D.gp.shift = 11;
+		D.gp.gmin[0] = -40;
+		D.gp.gmin[1] = 1ll << 50;
+		codes = gpcodes;
+		nbake = 3;
+	}
 	else if (!std::strcmp(shape, "lrepl"))
 	{
 		setenv("GG_PLAN_LREPL", "32", 1);
@@ -230,8 +248,8 @@ dump_shape(const char *shape, const char *file)
 		return false;
 	}
 
-	bool gn0 = D.gnulls[0] != nullptr;
-	gg_status s1 = plan_rtc_compile(D, gn0, false, &out);
+	bool gn0 = D.gnulls[0] != nullptr, gn1 = D.gnulls[1] != nullptr;
+	gg_status s1 = plan_rtc_compile(D, gn0, gn1, &out);
 	bool ok = compiled(s1);
 
 	if (!ok)
@@ -239,7 +257,7 @@ dump_shape(const char *shape, const char *file)
 			gg_engine_last_error());
 	if (nbake)
 	{
-		gg_status s2 = plan_rtc_compile(D, gn0, false, &out, codes,
+		gg_status s2 = plan_rtc_compile(D, gn0, gn1, &out, codes,
 						nbake, !wide);
 
 		if (!compiled(s2))
@@ -260,7 +278,7 @@ int
 main(int argc, char **argv)
 {
 	static const char *const all[] = {"q1", "q1w", "q6", "q1mm", "q1mmw",
-		"q6mm", "gn8", "g4", "join", "pnull", "lrepl"};
+		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl"};
 	const char *file = argc > 1 ? argv[1] : "/tmp/rtc_dump.cu";
 	const char *shape = argc > 2 ? argv[2] : "q1";
 	bool ok = true;
