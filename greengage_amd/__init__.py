@@ -12,6 +12,9 @@ from .engine import (  # noqa: F401
     JOIN_INNER,
     JOIN_SEMI,
     PGDate,
+    PLAN_MAX_FILTERS,
+    PLAN_MAX_FILTER_PREDS,
+    build_plan_desc,
     pgdate,
     plan_group_bits,
 )

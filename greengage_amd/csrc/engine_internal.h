@@ -7,6 +7,7 @@
 #define GG_ENGINE_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -646,6 +647,25 @@ struct PlanGroupPackDev
 	int64_t gmin[2];
 };
 
+/* Aggregate filters (engine_abi.h gg_plan_filter), appended after `gp`
+ * under the rule given at PlanPayloadDev: no field an existing plan reads
+ * may move, so a plan without a referenced filter keeps its kernels.
+ * Filter k keeps its descriptor index; `used` has bit k set iff some
+ * accumulator slot references it (only those are evaluated, once per
+ * row), afilt[a] is slot a's filter, 0 = none, 1+k = filter k.  A helper
+ * count slot carries its aggregate's filter.  The generated kernels read
+ * the block in place (P.fl; it is part of their argument bytes only when
+ * `used` is non-zero); the interpreted kernel gets a copy as an argument
+ * of its own (plan.hip PlFilters). */
+struct PlanFilterDev
+{
+	PlanPredDev preds[GG_PLAN_MAX_FILTERS][GG_PLAN_MAX_FILTER_PREDS];
+	int8_t psrc[GG_PLAN_MAX_FILTERS][GG_PLAN_MAX_FILTER_PREDS];
+	int8_t npreds[GG_PLAN_MAX_FILTERS];
+	int8_t afilt[GG_PLAN_MAX_AGGS];
+	int used;		/* bit k: filter k is referenced */
+};
+
 struct PlanDev
 {
 	int64_t n;
@@ -662,7 +682,12 @@ struct PlanDev
 	PlanAggDev aggs[GG_PLAN_MAX_AGGS];
 	PlanPayloadDev pl;
 	PlanGroupPackDev gp;
+	PlanFilterDev fl;
 };
+
+static_assert(offsetof(PlanDev, fl) ==
+	      offsetof(PlanDev, gp) + sizeof(PlanGroupPackDev),
+	      "PlanFilterDev follows PlanGroupPackDev without padding");
 
 struct PlanBuildDev
 {

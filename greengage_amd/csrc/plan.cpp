@@ -180,7 +180,8 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 	if (d->scan.npreds < 0 || d->scan.npreds > GG_PLAN_MAX_PREDS ||
 	    d->njoins < 0 || d->njoins > GG_PLAN_MAX_JOINS ||
 	    d->naggs < 1 || d->naggs > GG_PLAN_MAX_AGGS ||
-	    d->ngroup < 0 || d->ngroup > 2)
+	    d->ngroup < 0 || d->ngroup > 2 ||
+	    d->nfilters < 0 || d->nfilters > GG_PLAN_MAX_FILTERS)
 		return fail(GG_ENOTSUP, "plan: shape out of v1 bounds "
 			    "(fall back to standard_ExecutorRun)");
 
@@ -301,6 +302,28 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 	R->dev.gp.packed = d->ngroup == 2 &&
 		!(R->dev.gwidth[0] == 1 && R->dev.gwidth[1] == 1);
 
+	/* aggregate filters: every one is validated and resolved, referenced
+	 * or not; only the referenced ones (fl.used, set below) are ever
+	 * evaluated or counted in pred_bytes_per_row */
+	for (int k = 0; k < d->nfilters; k++)
+	{
+		const gg_plan_filter *F = &d->filters[k];
+
+		if (F->npreds < 0 || F->npreds > GG_PLAN_MAX_FILTER_PREDS)
+			return fail(GG_ENOTSUP, "plan: filter %d pred count", k);
+		R->dev.fl.npreds[k] = (int8_t) F->npreds;
+		for (int i = 0; i < F->npreds; i++)
+		{
+			Table *ft = nullptr;
+
+			GG_TRY(resolve_src(d, scan, F->src[i], d->njoins,
+					   "pred src of filter", k, &ft));
+			GG_TRY(resolve_pred(ft, &F->preds[i],
+					    &R->dev.fl.preds[k][i]));
+			R->dev.fl.psrc[k][i] = F->src[i];
+		}
+	}
+
 	int nacc = 0;
 	std::vector<int> helpers;	/* helper count slots so far */
 
@@ -312,6 +335,14 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		std::memset(&T, 0, sizeof(T));
 		if (A->kind < 0 || A->kind > GG_AGG_AVG)
 			return fail(GG_ENOTSUP, "plan: agg %d kind", a);
+		if (A->filter < 0 || A->filter > d->nfilters)
+			return fail(GG_EINVAL, "plan: agg %d names filter %d, "
+				    "the plan has %d", a, A->filter - 1,
+				    d->nfilters);
+		if (A->filter && d->filters[A->filter - 1].npreds == 0)
+			return fail(GG_EINVAL, "plan: agg %d references filter "
+				    "%d, which has no predicates", a,
+				    A->filter - 1);
 		if (A->kind == GG_AGG_COUNT_STAR)
 			T.nf = 0;
 		else if (A->nfactors < 1 || A->nfactors > 3 ||
@@ -354,6 +385,8 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 			R->dev.aggs[nacc].kind = devkind;
 			for (int f = 0; f < T.nf; f++)
 				R->dev.pl.asrc[nacc][f] = A->src[f];
+			/* a helper count inherits its aggregate's filter */
+			R->dev.fl.afilt[nacc] = A->filter;
 			return nacc++;
 		};
 		PlanResolved::OutAgg O{A->kind, -1, -1};
@@ -367,10 +400,12 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 			for (int h : helpers)
 			{
 				const PlanAggDev &H = R->dev.aggs[h];
-				bool same = H.nf == T.nf;
+				bool same = H.nf == T.nf &&
+					R->dev.fl.afilt[h] == A->filter;
 
-				/* same columns read at the same rows: a
-				 * table joined twice is two sources */
+				/* same columns read at the same rows, under
+				 * the same filter: a table joined twice is
+				 * two sources */
 				for (int f = 0; same && f < T.nf; f++)
 					same = H.col[f] == T.col[f] &&
 						R->dev.pl.asrc[h][f] == A->src[f];
@@ -392,6 +427,16 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		R->out_slots += A->kind == GG_AGG_AVG ? 2 : 1;
 	}
 	R->dev.naggs = nacc;
+	for (int a = 0; a < nacc; a++)
+		if (R->dev.fl.afilt[a])
+			R->dev.fl.used |= 1 << (R->dev.fl.afilt[a] - 1);
+	for (int k = 0; k < d->nfilters; k++)
+		if (R->dev.fl.used >> k & 1)
+			for (int i = 0; i < R->dev.fl.npreds[k]; i++)
+				R->pred_bytes_per_row +=
+					col_bytes(R->dev.fl.preds[k][i].col,
+						  R->dev.fl.psrc[k][i],
+						  R->dev.fl.preds[k][i].width);
 
 	Pipeline *p = new Pipeline();
 
@@ -467,7 +512,10 @@ plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
  * All values must be non-negative and
  * bound * rows_per_block must clear 2^61 with a
  * 4x margin (long double keeps int64 exact; the
- * margin absorbs product rounding). */
+ * margin absorbs product rounding).  An aggregate
+ * filter only removes inputs from a sum of
+ * non-negative values, so the whole-column bound
+ * holds for a filtered plan as it stands. */
 static bool
 plan_fast_tier_provable(Engine &e, const PlanResolved *R)
 {

@@ -19,6 +19,11 @@
  *                 (int8smaller/int8larger) are order-encoded so both
  *                 combine by unsigned max with 0 as identity
  *                 (engine_internal.h PlanAggDev)
+ *   agg filters   agg(...) FILTER (WHERE ...), the Aggref.aggfilter that
+ *                 advance_aggregates (nodeAgg.c) evaluates ahead of the
+ *                 strict transition: per-aggregate range conjunctions
+ *                 over driving or payload columns, evaluated once per
+ *                 surviving row; they never touch the groups
  *   agg exprs     products with (100±col) under numeric.c:1735 mul_var
  *                 scale addition (scaled-int exact arithmetic)
  *
@@ -492,6 +497,63 @@ pl_agg_val(const PlanAggDev &a, const int8_t *src, int64_t i,
 	}
 }
 
+/* FL = some aggregate carries a filter.  The kernel then gets the plan's
+ * PlanFilterDev as a kernel argument of its own and reads nothing of
+ * P.fl: every read of P counts against the compiler's limit (300 users)
+ * for serving a by-value argument straight from the kernarg segment, the
+ * PL = 1 kernels sit close to it, and past it the whole of P is copied to
+ * scratch and every column load turns flat (seen in the ISA: 2000 bytes
+ * of scratch, no global_load left).  Plans without a filter instantiate
+ * FL = 0, carry an empty argument, and compile to the code they always
+ * had. */
+template <int FL>
+struct PlFilters
+{
+};
+
+template <>
+struct PlFilters<1>
+{
+	PlanFilterDev f;
+};
+
+/* aggregate filters: every referenced filter once per surviving row, NULL
+ * flag first, into a bitmask (bit k = filter k is true).  Columns are
+ * read at the row their source names, so a payload predicate sees the
+ * joined build row. */
+template <int PL>
+__device__ static inline unsigned
+pl_row_filters(const PlanFilterDev &F, int64_t i, const PlRow<PL> &R)
+{
+	unsigned fm = 0;
+
+#pragma unroll
+	for (int k = 0; k < GG_PLAN_MAX_FILTERS; k++)
+	{
+		if (!((F.used >> k) & 1))
+			continue;
+		bool ok = true;
+
+		for (int q = 0; ok && q < F.npreds[k]; q++)
+		{
+			const PlanPredDev &C = F.preds[k][q];
+			const int64_t fi = pl_ix<PL>(R, F.psrc[k][q], i);
+
+			if (C.nulls && C.nulls[fi])
+				ok = false;	/* NULL comparison is not true */
+			else
+			{
+				int64_t v = pl_ld<0>(C.col, C.width, fi);
+
+				ok = v >= C.lo && v < C.hi;
+			}
+		}
+		if (ok)
+			fm |= 1u << k;
+	}
+	return fm;
+}
+
 static constexpr unsigned long long PL_EMPTY = 0x8000000000000000ull;
 
 /* group-table find-or-create (execHHashagg.c:905); -1 = table full */
@@ -550,15 +612,27 @@ pl_atomic_add128(unsigned long long *w, unsigned long long vlo,
 /* one row's transitions: every aggregate's value into its two-word
  * accumulator acc(a).  ATOMIC = the accumulators live in LDS
  * or global memory, else in registers.  Exact 128-bit add, or unsigned
- * max of the encoded MIN/MAX word. */
-template <int MM, int PL, bool ATOMIC, class Acc>
+ * max of the encoded MIN/MAX word.  FL = the plan references an
+ * aggregate filter: fm holds the row's filter bits and an aggregate whose
+ * filter bit is clear skips the row, ahead of everything else (COUNT(*)
+ * included).  Plans without one instantiate FL = 0 and compile to the
+ * code they always had. */
+template <int MM, int PL, int FL, bool ATOMIC, class Acc>
 __device__ static inline void
-pl_row_aggs(const PlanDev &P, int64_t i, const PlRow<PL> &R, Acc acc)
+pl_row_aggs(const PlanDev &P, const PlFilters<FL> &F, int64_t i,
+	    const PlRow<PL> &R, unsigned fm, Acc acc)
 {
 	for (int a = 0; a < P.naggs; a++)
 	{
 		__int128 v;
 
+		if constexpr (FL)
+		{
+			const int f = F.f.afilt[a];
+
+			if (f && !((fm >> (f - 1)) & 1))
+				continue;
+		}
 		if (!pl_agg_val<MM, PL>(P.aggs[a], P.pl.asrc[a], i, R, &v))
 			continue;
 		unsigned long long vlo = (unsigned long long) v;
@@ -602,9 +676,9 @@ pl_fold_flush(int kind, unsigned long long *dst, Rep rep)
 		pl_atomic_add128(dst, lo, hi);
 }
 
-template <int NT, int MM, int PL, int GP>
+template <int NT, int MM, int PL, int GP, int FL>
 __global__ __launch_bounds__(PL_THREADS, 4)
-void k_plan_scan_agg(PlanDev P)
+void k_plan_scan_agg(PlanDev P, PlFilters<FL> F)
 {
 	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
 
@@ -626,8 +700,12 @@ void k_plan_scan_agg(PlanDev P)
 
 			if (!pl_row_joins<PL>(P, i, R))
 				return;
-			pl_row_aggs<MM, PL, false>(P, i, R,
-						   [&](int a) { return acc[a]; });
+			unsigned fm = 0;
+
+			if constexpr (FL)
+				fm = pl_row_filters<PL>(F.f, i, R);
+			pl_row_aggs<MM, PL, FL, false>(P, F, i, R, fm,
+						       [&](int a) { return acc[a]; });
 		};
 		int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
 
@@ -706,6 +784,10 @@ void k_plan_scan_agg(PlanDev P)
 
 		if (!pl_row_joins<PL>(P, i, R))
 			return;
+		unsigned fm = 0;
+
+		if constexpr (FL)
+			fm = pl_row_filters<PL>(F.f, i, R);
 		long long code = pl_group_code<PL, GP>(P, i, R);
 		int ls = -1;
 		uint32_t pos = (uint32_t) gg_hashint8(code) & (LSLOTS - 1);
@@ -737,7 +819,7 @@ void k_plan_scan_agg(PlanDev P)
 		}
 		if (ls >= 0)
 		{
-			pl_row_aggs<MM, PL, true>(P, i, R, [&](int a)
+			pl_row_aggs<MM, PL, FL, true>(P, F, i, R, fm, [&](int a)
 			{
 				return &lvals[lrep][ls][2 * a];
 			});
@@ -751,7 +833,7 @@ void k_plan_scan_agg(PlanDev P)
 			atomicOr(P.err, PL_ERR_FULL);
 			return;
 		}
-		pl_row_aggs<MM, PL, true>(P, i, R, [&](int a)
+		pl_row_aggs<MM, PL, FL, true>(P, F, i, R, fm, [&](int a)
 		{
 			return &P.tvals[(slot * P.naggs + a) * 2];
 		});
@@ -792,6 +874,16 @@ void k_plan_scan_agg(PlanDev P)
 	}
 }
 
+template <int FL>
+static PlFilters<FL> pl_filters_arg(const PlanDev &p)
+{
+	PlFilters<FL> F;
+
+	if constexpr (FL)
+		F.f = p.fl;
+	return F;
+}
+
 hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
 {
 	const char *nt = getenv("GG_PLAN_NT");
@@ -808,27 +900,47 @@ hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
 			pl = true;
 	/* a packed pair of group columns (PlanGroupPackDev) */
 	const bool gp = p.ngroup == 2 && p.gp.packed;
-#define PL_LAUNCH(NT, MM, PL, GP) \
-	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL, GP>), \
-			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p)
-	switch ((gp ? 8 : 0) | (ntl ? 4 : 0) | (mm ? 2 : 0) | (pl ? 1 : 0))
+	/* some aggregate carries a filter (PlanFilterDev) */
+	const bool fl = p.fl.used != 0;
+#define PL_LAUNCH(NT, MM, PL, GP, FL) \
+	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL, GP, FL>), \
+			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p, \
+			   pl_filters_arg<FL>(p))
+	switch ((fl ? 16 : 0) | (gp ? 8 : 0) | (ntl ? 4 : 0) | (mm ? 2 : 0) |
+		(pl ? 1 : 0))
 	{
-		case 0: PL_LAUNCH(0, 0, 0, 0); break;
-		case 1: PL_LAUNCH(0, 0, 1, 0); break;
-		case 2: PL_LAUNCH(0, 1, 0, 0); break;
-		case 3: PL_LAUNCH(0, 1, 1, 0); break;
-		case 4: PL_LAUNCH(1, 0, 0, 0); break;
-		case 5: PL_LAUNCH(1, 0, 1, 0); break;
-		case 6: PL_LAUNCH(1, 1, 0, 0); break;
-		case 7: PL_LAUNCH(1, 1, 1, 0); break;
-		case 8: PL_LAUNCH(0, 0, 0, 1); break;
-		case 9: PL_LAUNCH(0, 0, 1, 1); break;
-		case 10: PL_LAUNCH(0, 1, 0, 1); break;
-		case 11: PL_LAUNCH(0, 1, 1, 1); break;
-		case 12: PL_LAUNCH(1, 0, 0, 1); break;
-		case 13: PL_LAUNCH(1, 0, 1, 1); break;
-		case 14: PL_LAUNCH(1, 1, 0, 1); break;
-		default: PL_LAUNCH(1, 1, 1, 1); break;
+		case 0: PL_LAUNCH(0, 0, 0, 0, 0); break;
+		case 1: PL_LAUNCH(0, 0, 1, 0, 0); break;
+		case 2: PL_LAUNCH(0, 1, 0, 0, 0); break;
+		case 3: PL_LAUNCH(0, 1, 1, 0, 0); break;
+		case 4: PL_LAUNCH(1, 0, 0, 0, 0); break;
+		case 5: PL_LAUNCH(1, 0, 1, 0, 0); break;
+		case 6: PL_LAUNCH(1, 1, 0, 0, 0); break;
+		case 7: PL_LAUNCH(1, 1, 1, 0, 0); break;
+		case 8: PL_LAUNCH(0, 0, 0, 1, 0); break;
+		case 9: PL_LAUNCH(0, 0, 1, 1, 0); break;
+		case 10: PL_LAUNCH(0, 1, 0, 1, 0); break;
+		case 11: PL_LAUNCH(0, 1, 1, 1, 0); break;
+		case 12: PL_LAUNCH(1, 0, 0, 1, 0); break;
+		case 13: PL_LAUNCH(1, 0, 1, 1, 0); break;
+		case 14: PL_LAUNCH(1, 1, 0, 1, 0); break;
+		case 15: PL_LAUNCH(1, 1, 1, 1, 0); break;
+		case 16: PL_LAUNCH(0, 0, 0, 0, 1); break;
+		case 17: PL_LAUNCH(0, 0, 1, 0, 1); break;
+		case 18: PL_LAUNCH(0, 1, 0, 0, 1); break;
+		case 19: PL_LAUNCH(0, 1, 1, 0, 1); break;
+		case 20: PL_LAUNCH(1, 0, 0, 0, 1); break;
+		case 21: PL_LAUNCH(1, 0, 1, 0, 1); break;
+		case 22: PL_LAUNCH(1, 1, 0, 0, 1); break;
+		case 23: PL_LAUNCH(1, 1, 1, 0, 1); break;
+		case 24: PL_LAUNCH(0, 0, 0, 1, 1); break;
+		case 25: PL_LAUNCH(0, 0, 1, 1, 1); break;
+		case 26: PL_LAUNCH(0, 1, 0, 1, 1); break;
+		case 27: PL_LAUNCH(0, 1, 1, 1, 1); break;
+		case 28: PL_LAUNCH(1, 0, 0, 1, 1); break;
+		case 29: PL_LAUNCH(1, 0, 1, 1, 1); break;
+		case 30: PL_LAUNCH(1, 1, 0, 1, 1); break;
+		default: PL_LAUNCH(1, 1, 1, 1, 1); break;
 	}
 #undef PL_LAUNCH
 	return hipGetLastError();

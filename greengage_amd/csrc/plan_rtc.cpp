@@ -48,7 +48,10 @@ struct PlanRtc
  * emit_prelude: the trailing PlanGroupPackDev block exists only in the
  * program of a plan with a packed pair of group columns, so every other
  * plan's kernel keeps the argument block, and with it the binary, it
- * always had (plan_rtc_launch passes that many bytes) */
+ * always had (plan_rtc_launch passes that many bytes).  A plan that
+ * references an aggregate filter gets both trailing blocks, `gp` and the
+ * PlanFilterDev after it, through the same two macros, so this text and
+ * with it every other plan's program stays byte for byte what it was */
 static const char *STRUCT_DEFS = R"GG(
 typedef long long int64_t;
 typedef unsigned long long uint64_t;
@@ -312,9 +315,17 @@ static bool packed_args(const PlanDev &D)
 	return D.ngroup == 2 && D.gp.packed;
 }
 
+/* a plan with a referenced aggregate filter reads PlanDev.fl, the last
+ * block, and so carries `gp` too */
+static bool filter_args(const PlanDev &D)
+{
+	return D.fl.used != 0;
+}
+
 static size_t plan_arg_bytes(const PlanDev &D)
 {
-	return packed_args(D) ? sizeof(PlanDev) : offsetof(PlanDev, gp);
+	return filter_args(D) ? sizeof(PlanDev)
+		: packed_args(D) ? offsetof(PlanDev, fl) : offsetof(PlanDev, gp);
 }
 
 /* the row index a column of source `src` is loaded at: the driving row,
@@ -329,7 +340,14 @@ static void emit_prelude(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
 
-	s += packed_args(D)
+	s += filter_args(D)
+		? "#define GP_STRUCT struct PlanGroupPackDev "
+		  "{ int packed; int shift; int64_t gmin[2]; }; "
+		  "struct PlanFilterDev { PlanPredDev preds[4][4]; "
+		  "int8_t psrc[4][4]; int8_t npreds[4]; int8_t afilt[8]; "
+		  "int used; };\n"
+		  "#define GP_MEMBER PlanGroupPackDev gp; PlanFilterDev fl;\n"
+		: packed_args(D)
 		? "#define GP_STRUCT struct PlanGroupPackDev "
 		  "{ int packed; int shift; int64_t gmin[2]; };\n"
 		  "#define GP_MEMBER PlanGroupPackDev gp;\n"
@@ -356,12 +374,22 @@ static void emit_prelude(std::string &s, const Gen &G)
 		 sizeof(PlanPayloadDev), offsetof(PlanDev, pl),
 		 offsetof(PlanPayloadDev, jkind),
 		 offsetof(PlanPayloadDev, asrc));
-	if (packed_args(D))
+	if (packed_args(D) || filter_args(D))
 		s += fmt("static_assert(sizeof(PlanGroupPackDev) == %zu, \"layout\");\n"
 			 "static_assert(__builtin_offsetof(PlanDev, gp) == %zu, \"layout\");\n"
 			 "static_assert(__builtin_offsetof(PlanGroupPackDev, gmin) == %zu, \"layout\");\n",
 			 sizeof(PlanGroupPackDev), offsetof(PlanDev, gp),
 			 offsetof(PlanGroupPackDev, gmin));
+	if (filter_args(D))
+		s += fmt("static_assert(sizeof(PlanFilterDev) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanDev, fl) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanFilterDev, psrc) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanFilterDev, afilt) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanFilterDev, used) == %zu, \"layout\");\n",
+			 sizeof(PlanFilterDev), offsetof(PlanDev, fl),
+			 offsetof(PlanFilterDev, psrc),
+			 offsetof(PlanFilterDev, afilt),
+			 offsetof(PlanFilterDev, used));
 
 	/* baked variant: more replicas by default — the accumulator
 	 * array has only nbake slots, so per-word contention is higher
@@ -397,14 +425,16 @@ static void emit_prelude(std::string &s, const Gen &G)
 	 * on the same shape). */
 	s += G.fast ? "#define LW 1\n" : "#define LW 2\n";
 	{
-		bool nn = true;
+		/* a filtered aggregate's flag starts from its filter */
+		bool nn = !filter_args(D);
 
 		for (int a = 0; a < D.naggs; a++)
 			for (int f = 0; f < D.aggs[a].nf; f++)
 				if (D.aggs[a].nulls[f])
 					nn = false;
 		/* strict-transition flags vanish at compile time when
-		 * no aggregate input is nullable (the common case) */
+		 * no aggregate input is nullable and no aggregate is
+		 * filtered (the common case) */
 		s += nn ? "#define AOK(a) true\n"
 			: "#define AOK(a) (aok[a])\n";
 	}
@@ -492,7 +522,14 @@ static void emit_row_pass(std::string &s, const Gen &G)
  * hand-written k_q1_agg issues 7 (measured via offline ISA
  * dump, tools/rtc_dump_local.cpp).  A load is one (pointer, width,
  * source): a table joined twice as INNER is two sources, and its
- * columns are then read at two different build rows. */
+ * columns are then read at two different build rows.
+ *
+ * Aggregate filters (PlanFilterDev): their predicate columns go through
+ * the same load table, so a column that is both a factor and a filter
+ * input is loaded once; each referenced filter k becomes one branch-free
+ * `bool flt<k>` per row, and a filtered aggregate's aok[a] starts from
+ * it instead of `true`.  emit_transitions gates every destination on
+ * AOK(a), so nothing downstream knows about filters. */
 static void emit_agg_vals(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
@@ -502,23 +539,25 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 		int width, src;
 	};
 	std::vector<Ld> uniq;
-	auto var_of = [&](int a, int f) -> int
+	auto var_ld = [&](const void *c, int w, int src,
+			  const std::string &ptr) -> int
 	{
-		const void *c = D.aggs[a].col[f];
-		int w = D.aggs[a].width[f];
-		int src = D.pl.asrc[a][f];
-
 		for (size_t u = 0; u < uniq.size(); u++)
 			if (uniq[u].col == c && uniq[u].width == w &&
 			    uniq[u].src == src)
 				return (int) u;
 		uniq.push_back({c, w, src});
 		emit_ld(s, fmt("xu%d", (int) uniq.size() - 1).c_str(),
-			fmt("P.aggs[%d].col[%d]", a, f).c_str(), w,
-			ix_of(D.pl.asrc[a][f]).c_str(),
+			ptr.c_str(), w, ix_of(src).c_str(),
 			/* gathered payload loads are never nontemporal */
-			G.nt && !D.pl.asrc[a][f]);
+			G.nt && !src);
 		return (int) uniq.size() - 1;
+	};
+	auto var_of = [&](int a, int f) -> int
+	{
+		return var_ld(D.aggs[a].col[f], D.aggs[a].width[f],
+			      D.pl.asrc[a][f],
+			      fmt("P.aggs[%d].col[%d]", a, f));
 	};
 	/* the factor as it enters a product: the loaded var or its
 	 * (100±) term */
@@ -567,15 +606,49 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 						 u, m, m == 1 ? '-' : '+', u);
 				}
 	}
+	/* pass 1c: every referenced filter once, branch-free like the
+	 * strided predicate streams: range test on the loaded value, AND the
+	 * NULL flag where the column has one (the value under a set flag is
+	 * loaded and ignored) */
+	for (int k = 0; k < GG_PLAN_MAX_FILTERS; k++)
+	{
+		if (!((D.fl.used >> k) & 1))
+			continue;
+		std::string e;
+
+		for (int q = 0; q < D.fl.npreds[k]; q++)
+		{
+			const PlanPredDev &F = D.fl.preds[k][q];
+			int src = D.fl.psrc[k][q];
+			int u = var_ld(F.col, F.width, src,
+				       fmt("P.fl.preds[%d][%d].col", k, q));
+
+			e += fmt("%s(xu%d >= P.fl.preds[%d][%d].lo) & "
+				 "(xu%d < P.fl.preds[%d][%d].hi)",
+				 q ? "\n\t\t\t& " : "", u, k, q, u, k, q);
+			if (F.nulls)
+				e += fmt(" & !P.fl.preds[%d][%d].nulls[%s]", k, q,
+					 ix_of(src).c_str());
+		}
+		s += fmt("\t\tbool flt%d = %s;\n", k, e.c_str());
+	}
+	/* the flag an aggregate's strict rule starts from */
+	auto aok0 = [&](int a) -> std::string
+	{
+		return D.fl.afilt[a] ? fmt("flt%d", D.fl.afilt[a] - 1)
+			: std::string("true");
+	};
+
 	/* pass 2: per-agg strict flags + products over the shared vars */
 	for (int a = 0; a < D.naggs; a++)
 	{
 		if (D.aggs[a].kind == 0)
 		{
-			s += fmt("\t\tav[%d] = 1; aok[%d] = true;\n", a, a);
+			s += fmt("\t\tav[%d] = 1; aok[%d] = %s;\n", a, a,
+				 aok0(a).c_str());
 			continue;
 		}
-		s += fmt("\t\taok[%d] = true;\n", a);
+		s += fmt("\t\taok[%d] = %s;\n", a, aok0(a).c_str());
 		for (int f = 0; f < D.aggs[a].nf; f++)
 			if (D.aggs[a].nulls[f])
 				s += fmt("\t\tif (P.aggs[%d].nulls[%d][%s]) aok[%d] = false;\n",

@@ -59,7 +59,17 @@ class _PlanJoin(ctypes.Structure):
 class _PlanAgg(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_int), ("nfactors", ctypes.c_int),
                 ("col", ctypes.c_char_p * 3), ("mod", ctypes.c_int8 * 3),
-                ("src", ctypes.c_int8 * 3)]
+                ("src", ctypes.c_int8 * 3), ("filter", ctypes.c_int8)]
+
+
+PLAN_MAX_FILTERS = 4          # GG_PLAN_MAX_FILTERS
+PLAN_MAX_FILTER_PREDS = 4     # GG_PLAN_MAX_FILTER_PREDS
+
+
+class _PlanFilter(ctypes.Structure):
+    _fields_ = [("preds", _PlanPred * PLAN_MAX_FILTER_PREDS),
+                ("src", ctypes.c_int8 * PLAN_MAX_FILTER_PREDS),
+                ("npreds", ctypes.c_int)]
 
 
 class _PlanDesc(ctypes.Structure):
@@ -67,7 +77,9 @@ class _PlanDesc(ctypes.Structure):
                 ("njoins", ctypes.c_int),
                 ("group_cols", ctypes.c_char_p * 2),
                 ("ngroup", ctypes.c_int), ("aggs", _PlanAgg * 8),
-                ("naggs", ctypes.c_int), ("group_src", ctypes.c_int8 * 2)]
+                ("naggs", ctypes.c_int), ("group_src", ctypes.c_int8 * 2),
+                ("filters", _PlanFilter * PLAN_MAX_FILTERS),
+                ("nfilters", ctypes.c_int)]
 
 
 NEG_INF = -(1 << 63)          # one-sided range bounds
@@ -78,6 +90,131 @@ AGG_COUNT_STAR, AGG_COUNT_COL, AGG_SUM = 0, 1, 2
 AGG_MIN, AGG_MAX, AGG_AVG = 3, 4, 5
 # gg_plan_joinkind (engine_abi.h)
 JOIN_SEMI, JOIN_INNER = 0, 1
+
+
+def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
+                    aggs=()):
+    """The gg_plan_desc (engine_abi.h) of a compositional plan and the
+    aggregate kinds execute_plan decodes by: (desc, kinds).  Pure: calls
+    neither the library nor a GPU.
+
+    preds: [(col, lo, hi)]  (half-open; NEG_INF/POS_INF one-sided)
+    joins: [{"table": h, "build_key": c, "probe_key": c,
+             "preds": [...], "kind": "semi"|"inner",
+             "probe_src": k}]
+           "semi" (default) is a filter; "inner" joins a
+           unique-keyed build table whose columns the plan can then
+           read.  probe_src k takes probe_key from the build table
+           of the earlier INNER join k-1 (0 = driving table).
+    group_cols: 0-2 columns of any accepted type (char1, int32,
+           int64) and source.  Two char1 columns keep their fixed
+           code; any other pair is packed into one 64-bit code by
+           the columns' value ranges and must fit 62 bits
+           (plan_group_bits).  The ranges are resolved at the first
+           execute_plan, which raises EngineError status 5 for a
+           pair that does not fit.
+    aggs: ["count"] | ("count", col) |
+          ("sum", [(col, "id"|"sub100"|"add100"), ...]) |
+          ("min", (col, mod)) | ("max", (col, mod)) |
+          ("avg", [(col, mod), ...]) |
+          ("filter", <any of the above>, [(col, lo, hi), ...])
+          The last form is agg(...) FILTER (WHERE ...): the aggregate
+          sees only the surviving rows on which every half-open range
+          holds (a NULL value fails it).  Groups are unaffected; a group
+          with no passing row reports COUNT 0, SUM 0, MIN/MAX None,
+          AVG (0, 0).  Equal predicate lists share one entry of the
+          descriptor's filters[]; more than PLAN_MAX_FILTERS distinct
+          lists, or more than PLAN_MAX_FILTER_PREDS ranges in one, raise
+          ValueError.
+    A group column, aggregate factor or filter `col` is a column name of
+    the driving table, or a pair (join_index, name) for a column of
+    that INNER join's build table.
+    """
+    mods = {"id": 0, "sub100": 1, "add100": 2}
+    jkinds = {"semi": JOIN_SEMI, "inner": JOIN_INNER}
+
+    def colref(c):
+        """(name bytes, source): 0 = driving, 1+k = join k"""
+        if isinstance(c, str):
+            return c.encode(), 0
+        k, name = c
+        return name.encode(), 1 + k
+
+    def fill_scan(dst, table, plist):
+        dst.table = table
+        dst.npreds = len(plist)
+        for i, (c, lo, hi) in enumerate(plist):
+            dst.preds[i].col = c.encode()
+            dst.preds[i].lo = lo
+            dst.preds[i].hi = hi
+
+    d = _PlanDesc()
+    fill_scan(d.scan, scan_table, list(preds))
+    d.njoins = len(joins)
+    for j, spec in enumerate(joins):
+        fill_scan(d.joins[j].build, spec["table"],
+                  list(spec.get("preds", ())))
+        d.joins[j].build_key = spec["build_key"].encode()
+        d.joins[j].probe_key = spec["probe_key"].encode()
+        d.joins[j].kind = jkinds[spec.get("kind", "semi")]
+        d.joins[j].probe_src = spec.get("probe_src", 0)
+    d.ngroup = len(group_cols)
+    for g, c in enumerate(group_cols):
+        d.group_cols[g], d.group_src[g] = colref(c)
+    d.naggs = len(aggs)
+    kinds = []
+    filters = []                 # distinct predicate lists, in order
+    for a, spec in enumerate(aggs):
+        if isinstance(spec, (tuple, list)) and spec[0] == "filter":
+            _tag, spec, fpreds = spec
+            key = tuple((colref(c), int(lo), int(hi))
+                        for c, lo, hi in fpreds)
+            if len(key) > PLAN_MAX_FILTER_PREDS:
+                raise ValueError(
+                    f"aggregate {a}: a filter holds at most "
+                    f"{PLAN_MAX_FILTER_PREDS} predicates")
+            if key not in filters:
+                if len(filters) == PLAN_MAX_FILTERS:
+                    raise ValueError(
+                        f"aggregate {a}: more than {PLAN_MAX_FILTERS} "
+                        "distinct filters in one plan")
+                filters.append(key)
+            d.aggs[a].filter = 1 + filters.index(key)
+        if spec == "count" or spec == ("count",):
+            d.aggs[a].kind = AGG_COUNT_STAR
+            d.aggs[a].nfactors = 0
+        elif spec[0] == "count":
+            d.aggs[a].kind = AGG_COUNT_COL
+            d.aggs[a].nfactors = 1
+            d.aggs[a].col[0], d.aggs[a].src[0] = colref(spec[1])
+            d.aggs[a].mod[0] = 0
+        elif spec[0] in ("min", "max"):
+            # exactly one factor; a factor LIST is passed through
+            # so the engine's nfactors != 1 rejection is reachable
+            fs = ([spec[1]] if len(spec[1]) == 2 and
+                  isinstance(spec[1][1], str) else list(spec[1]))
+            d.aggs[a].kind = AGG_MIN if spec[0] == "min" else AGG_MAX
+            d.aggs[a].nfactors = len(fs)
+            for f, (c, m) in enumerate(fs):
+                d.aggs[a].col[f], d.aggs[a].src[f] = colref(c)
+                d.aggs[a].mod[f] = mods[m]
+        else:
+            assert spec[0] in ("sum", "avg"), spec
+            d.aggs[a].kind = AGG_SUM if spec[0] == "sum" else AGG_AVG
+            d.aggs[a].nfactors = len(spec[1])
+            for f, (c, m) in enumerate(spec[1]):
+                d.aggs[a].col[f], d.aggs[a].src[f] = colref(c)
+                d.aggs[a].mod[f] = mods[m]
+        kinds.append(d.aggs[a].kind)
+    d.nfilters = len(filters)
+    for k, key in enumerate(filters):
+        d.filters[k].npreds = len(key)
+        for i, ((name, src), lo, hi) in enumerate(key):
+            d.filters[k].preds[i].col = name
+            d.filters[k].preds[i].lo = lo
+            d.filters[k].preds[i].hi = hi
+            d.filters[k].src[i] = src
+    return d, kinds
 
 
 class KernelStat(ctypes.Structure):
@@ -410,91 +547,10 @@ class Engine:
     # ---- generalized pipeline descriptor (v2) ----
     def compile_plan(self, scan_table, preds=(), joins=(), group_cols=(),
                      aggs=()):
-        """Compile a compositional plan (engine_abi.h gg_plan_desc).
-
-        preds: [(col, lo, hi)]  (half-open; NEG_INF/POS_INF one-sided)
-        joins: [{"table": h, "build_key": c, "probe_key": c,
-                 "preds": [...], "kind": "semi"|"inner",
-                 "probe_src": k}]
-               "semi" (default) is a filter; "inner" joins a
-               unique-keyed build table whose columns the plan can then
-               read.  probe_src k takes probe_key from the build table
-               of the earlier INNER join k-1 (0 = driving table).
-        group_cols: 0-2 columns of any accepted type (char1, int32,
-               int64) and source.  Two char1 columns keep their fixed
-               code; any other pair is packed into one 64-bit code by
-               the columns' value ranges and must fit 62 bits
-               (plan_group_bits).  The ranges are resolved at the first
-               execute_plan, which raises EngineError status 5 for a
-               pair that does not fit.
-        aggs: ["count"] | ("count", col) |
-              ("sum", [(col, "id"|"sub100"|"add100"), ...]) |
-              ("min", (col, mod)) | ("max", (col, mod)) |
-              ("avg", [(col, mod), ...])
-        A group column or aggregate factor `col` is a column name of
-        the driving table, or a pair (join_index, name) for a column of
-        that INNER join's build table.
-        """
-        mods = {"id": 0, "sub100": 1, "add100": 2}
-        jkinds = {"semi": JOIN_SEMI, "inner": JOIN_INNER}
-
-        def colref(c):
-            """(name bytes, source): 0 = driving, 1+k = join k"""
-            if isinstance(c, str):
-                return c.encode(), 0
-            k, name = c
-            return name.encode(), 1 + k
-
-        def fill_scan(dst, table, plist):
-            dst.table = table
-            dst.npreds = len(plist)
-            for i, (c, lo, hi) in enumerate(plist):
-                dst.preds[i].col = c.encode()
-                dst.preds[i].lo = lo
-                dst.preds[i].hi = hi
-
-        d = _PlanDesc()
-        fill_scan(d.scan, scan_table, list(preds))
-        d.njoins = len(joins)
-        for j, spec in enumerate(joins):
-            fill_scan(d.joins[j].build, spec["table"],
-                      list(spec.get("preds", ())))
-            d.joins[j].build_key = spec["build_key"].encode()
-            d.joins[j].probe_key = spec["probe_key"].encode()
-            d.joins[j].kind = jkinds[spec.get("kind", "semi")]
-            d.joins[j].probe_src = spec.get("probe_src", 0)
-        d.ngroup = len(group_cols)
-        for g, c in enumerate(group_cols):
-            d.group_cols[g], d.group_src[g] = colref(c)
-        d.naggs = len(aggs)
-        kinds = []
-        for a, spec in enumerate(aggs):
-            if spec == "count" or spec == ("count",):
-                d.aggs[a].kind = AGG_COUNT_STAR
-                d.aggs[a].nfactors = 0
-            elif spec[0] == "count":
-                d.aggs[a].kind = AGG_COUNT_COL
-                d.aggs[a].nfactors = 1
-                d.aggs[a].col[0], d.aggs[a].src[0] = colref(spec[1])
-                d.aggs[a].mod[0] = 0
-            elif spec[0] in ("min", "max"):
-                # exactly one factor; a factor LIST is passed through
-                # so the engine's nfactors != 1 rejection is reachable
-                fs = ([spec[1]] if len(spec[1]) == 2 and
-                      isinstance(spec[1][1], str) else list(spec[1]))
-                d.aggs[a].kind = AGG_MIN if spec[0] == "min" else AGG_MAX
-                d.aggs[a].nfactors = len(fs)
-                for f, (c, m) in enumerate(fs):
-                    d.aggs[a].col[f], d.aggs[a].src[f] = colref(c)
-                    d.aggs[a].mod[f] = mods[m]
-            else:
-                assert spec[0] in ("sum", "avg"), spec
-                d.aggs[a].kind = AGG_SUM if spec[0] == "sum" else AGG_AVG
-                d.aggs[a].nfactors = len(spec[1])
-                for f, (c, m) in enumerate(spec[1]):
-                    d.aggs[a].col[f], d.aggs[a].src[f] = colref(c)
-                    d.aggs[a].mod[f] = mods[m]
-            kinds.append(d.aggs[a].kind)
+        """Compile a compositional plan (engine_abi.h gg_plan_desc); the
+        arguments are build_plan_desc's."""
+        d, kinds = build_plan_desc(scan_table, preds, joins, group_cols,
+                                   aggs)
         h = I32()
         _check(lib().gg_engine_compile_plan(ctypes.byref(d),
                                             ctypes.byref(h)), "compile_plan")

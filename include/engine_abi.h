@@ -436,7 +436,11 @@ gg_status gg_engine_radix_sort_u64(uint64_t *keys, uint64_t *payload_or_null,
  * column factors with the (100±col) scaled-decimal modifiers TPC-H
  * money expressions need (numeric.c:1735 mul_var dscale rule;
  * ExecTargetList execQual.c:6369), plus MIN/MAX over one such factor
- * (int8smaller/int8larger).  Q1/Q3/Q5-shaped descriptors keep their
+ * (int8smaller/int8larger).  Every aggregate may carry its own FILTER
+ * (WHERE ...) conjunction, the aggregate filter advance_aggregates
+ * (nodeAgg.c) evaluates ahead of the strict transition: conditional
+ * aggregation, pivots, SUM(CASE WHEN c THEN x ELSE 0 END).
+ * Q1/Q3/Q5-shaped descriptors keep their
  * specialized kernels via gg_engine_compile_pipeline; everything else
  * — mpph6 (Q6), changed predicate columns, ad-hoc scans — compiles
  * here with ZERO query-specific kernels.  Unsupported shapes return
@@ -445,6 +449,8 @@ gg_status gg_engine_radix_sort_u64(uint64_t *keys, uint64_t *payload_or_null,
 #define GG_PLAN_MAX_PREDS 8
 #define GG_PLAN_MAX_JOINS 2
 #define GG_PLAN_MAX_AGGS 8
+#define GG_PLAN_MAX_FILTERS 4
+#define GG_PLAN_MAX_FILTER_PREDS 4
 
 /* conjunct: lo <= col < hi (INT64_MIN/INT64_MAX = one-sided; equality
  * = [v, v+1)).  A NULL column value fails the qual (SQL three-valued
@@ -465,7 +471,8 @@ typedef struct gg_plan_scan
 
 /* Column sources.  Wherever a descriptor names a column that is read
  * per driving row (a join's probe_key, a group column, an aggregate
- * factor) a source byte beside it names the table the column belongs
+ * factor, an aggregate filter's predicate column) a source byte beside
+ * it names the table the column belongs
  * to: 0 = the driving table (today's meaning, and what a
  * zero-initialised descriptor says), 1+k = the build table of join k,
  * which must be a GG_JOIN_INNER join (for a probe_src: one with a lower
@@ -548,7 +555,53 @@ typedef struct gg_plan_agg
 	const char *col[3];
 	int8_t mod[3];		/* gg_plan_fmod */
 	int8_t src[3];		/* source of col[f] (column sources above) */
+	int8_t filter;		/* 0 = none, 1+k = desc.filters[k] (below) */
 } gg_plan_agg;
+
+/* Aggregate filter: agg(...) FILTER (WHERE p0 AND p1 ...), the
+ * Aggref.aggfilter that advance_aggregates (nodeAgg.c) evaluates before
+ * the strict transition.  Filters are a table on the descriptor, so that
+ * several aggregates can share one condition and have it evaluated once
+ * per row; gg_plan_agg.filter picks one.
+ *
+ * A filter is evaluated per driving row that survived the WHERE
+ * predicates and all joins.  It never changes which rows survive and
+ * never changes which groups exist.  Its predicate columns follow the
+ * "column sources" rule: src[i] = 0 is the driving table, 1+k the build
+ * table of INNER join k, read at the joined build row.  A conjunct over
+ * a NULL column value is not true, as for WHERE; a payload column's NULL
+ * flag is read at the build row.  The aggregate then skips the row.
+ *
+ * Aggregate a transitions on a row iff its filter is true AND its
+ * strict-input rule holds; COUNT(*) with a filter counts the rows where
+ * the filter is true.  A group none of whose rows pass a filter still
+ * appears, and that aggregate reports
+ *   COUNT    0
+ *   SUM      slot = 0: the convention for a SUM with no non-NULL input.
+ *            A caller who needs FILTER's SQL NULL pairs the SUM with a
+ *            COUNT under the same filter (COUNT = 0 means NULL)
+ *   MIN/MAX  hi == 0, i.e. SQL NULL
+ *   AVG      N = 0
+ * and a plain aggregate (ngroup == 0) still yields exactly one row.
+ * SUM(CASE WHEN c THEN x ELSE 0 END) and COUNT(CASE WHEN c THEN 1 END)
+ * map onto a filtered SUM / COUNT(*), with that one difference (0 where
+ * FILTER says NULL).
+ *
+ * Errors: gg_plan_agg.filter outside [0, nfilters] is GG_EINVAL;
+ * nfilters outside [0, GG_PLAN_MAX_FILTERS] or a filter's npreds >
+ * GG_PLAN_MAX_FILTER_PREDS (or < 0) is GG_ENOTSUP; a filter an aggregate
+ * references with npreds == 0 is GG_EINVAL; a missing column, or a
+ * source naming a SEMI join or a join >= njoins, is GG_EINVAL as for
+ * factors.  A filter no aggregate references is validated the same way
+ * and otherwise ignored: it costs no loads and no code. */
+typedef struct gg_plan_filter
+{
+	gg_plan_pred preds[GG_PLAN_MAX_FILTER_PREDS];	/* conjunction,
+							 * lo <= col < hi */
+	int8_t src[GG_PLAN_MAX_FILTER_PREDS];	/* column source of
+						 * preds[i].col */
+	int npreds;
+} gg_plan_filter;
 
 typedef struct gg_plan_desc
 {
@@ -590,7 +643,19 @@ typedef struct gg_plan_desc
 	int naggs;
 	int8_t group_src[2];	/* source of group_cols[g] (column sources
 				 * above) */
+	/* aggregate filters (gg_plan_filter above); a zero-initialised
+	 * tail means what a descriptor without it meant */
+	gg_plan_filter filters[GG_PLAN_MAX_FILTERS];
+	int nfilters;
 } gg_plan_desc;
+
+#ifdef __cplusplus
+static_assert(sizeof(gg_plan_agg) == 2 * sizeof(int) + 3 * sizeof(char *) + 8,
+	      "gg_plan_agg.filter must sit in the tail padding");
+#else
+_Static_assert(sizeof(gg_plan_agg) == 2 * sizeof(int) + 3 * sizeof(char *) + 8,
+	       "gg_plan_agg.filter must sit in the tail padding");
+#endif
 
 #define GG_PLAN_NULL_KEY (-9223372036854775807LL)	/* INT64_MIN+1 */
 
@@ -613,9 +678,10 @@ typedef struct gg_plan_desc
  * Accumulator budget: on the device every aggregate occupies
  * accumulator slots, GG_PLAN_MAX_AGGS in all.  COUNT and SUM take one;
  * MIN and MAX take a value word plus a non-NULL count; AVG takes a sum
- * plus a count.  The helper counts of MIN/MAX/AVG aggregates over the
- * same factor columns are shared.  A descriptor whose lowered form
- * needs more than GG_PLAN_MAX_AGGS slots returns GG_ENOTSUP; any
+ * plus a count.  The helper counts of MIN/MAX/AVG aggregates are shared
+ * only when the factor columns, their sources and the filter index all
+ * match (a helper count inherits its aggregate's filter).  A descriptor
+ * whose lowered form needs more than GG_PLAN_MAX_AGGS slots returns GG_ENOTSUP; any
  * descriptor with 4 or fewer aggregates compiles. */
 gg_status gg_engine_compile_plan(const gg_plan_desc *desc, gg_pipeline *out);
 

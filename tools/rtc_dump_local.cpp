@@ -25,6 +25,12 @@
  *          pair: generic + baked fast tier
  *   lrepl  q1mmw's 8 two-word aggregates under GG_PLAN_LREPL=32, which
  *          the LDS budget shrinks back to 16 replicas
+ *   q1f    Q1 shape with aggregate filters: sum(price) and
+ *          sum(price*(100-disc)) share filter 0 (disc in a range, a column
+ *          that is also a factor), COUNT(*) carries filter 1 (qty < k);
+ *          generic + baked fast tier
+ *   pvf    global-group plan with one dense INNER join whose payload
+ *          column feeds two filters over the same SUM factors (a pivot)
  *   all    every shape above, DUMPFILE used as a prefix: <prefix><shape>.cu
  * Exit status is non-zero when a variant fails to COMPILE (a module
  * load / function lookup failure without a GPU is not a failure). */
@@ -157,6 +163,28 @@ shape_g1(PlanDev &D, int width, bool nullable)
 	set_agg(D, 2, 2, 2, c_pd, m_id);
 }
 
+/* filter k, conjunct q: lo <= column at dummy + col (of source src) < hi */
+static void
+set_fpred(PlanDev &D, int k, int q, int col, int width, int src,
+	  int64_t lo, int64_t hi)
+{
+	D.fl.preds[k][q].col = dummy + col;
+	D.fl.preds[k][q].width = width;
+	D.fl.preds[k][q].lo = lo;
+	D.fl.preds[k][q].hi = hi;
+	D.fl.psrc[k][q] = (int8_t) src;
+	if (D.fl.npreds[k] < q + 1)
+		D.fl.npreds[k] = (int8_t) (q + 1);
+}
+
+/* slot a carries filter k, as plan.cpp lowers gg_plan_agg.filter */
+static void
+set_afilt(PlanDev &D, int a, int k)
+{
+	D.fl.afilt[a] = (int8_t) (1 + k);
+	D.fl.used |= 1 << k;
+}
+
 /* compile errors come back as GG_ENOTSUP with this message prefix */
 static bool
 compiled(gg_status s)
@@ -184,6 +212,40 @@ dump_shape(const char *shape, const char *file)
 	unsetenv("GG_PLAN_LREPL");
 	if (!std::strncmp(shape, "q6", 2))
 		shape_q6(D, mm);
+	else if (!std::strcmp(shape, "q1f"))
+	{
+		shape_q1(D, false);
+		set_fpred(D, 0, 0, DISC, 8, 0, 5, 8);
+		set_fpred(D, 1, 0, QTY, 8, 0, INT64_MIN, 2400);
+		set_afilt(D, 2, 0);
+		set_afilt(D, 4, 0);
+		set_afilt(D, 0, 1);
+		codes = q1codes;
+		nbake = 6;
+	}
+	else if (!std::strcmp(shape, "pvf"))
+	{
+		static const int c_pd[] = {PRICE, DISC};
+		static const int m_pd[] = {0, 1};
+
+		shape_q6(D, false);
+		D.npreds = 1;
+		D.njoins = 1;
+		D.joins[0].pkey = dummy + 144;
+		D.joins[0].width = 8;
+		D.joins[0].dlen = 1000;
+		D.pl.jkind[0] = GG_JOIN_INNER;
+		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
+		D.naggs = 3;
+		set_agg(D, 0, 2, 2, c_pd, m_pd);
+		set_agg(D, 1, 2, 2, c_pd, m_pd);
+		set_agg(D, 2, 2, 2, c_pd, m_pd);
+		/* o_orderdate (int32) of the joined orders row, two years */
+		set_fpred(D, 0, 0, 200, 4, 1, 8035, 8401);
+		set_fpred(D, 1, 0, 200, 4, 1, 8401, 8766);
+		set_afilt(D, 0, 0);
+		set_afilt(D, 1, 1);
+	}
 	else if (!std::strncmp(shape, "q1", 2))
 	{
 		shape_q1(D, mm);
@@ -278,7 +340,7 @@ int
 main(int argc, char **argv)
 {
 	static const char *const all[] = {"q1", "q1w", "q6", "q1mm", "q1mmw",
-		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl"};
+		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl", "q1f", "pvf"};
 	const char *file = argc > 1 ? argv[1] : "/tmp/rtc_dump.cu";
 	const char *shape = argc > 2 ? argv[2] : "q1";
 	bool ok = true;
