@@ -9,7 +9,9 @@ unloadable engine library raises immediately.
 from .engine import (  # noqa: F401
     Engine,
     EngineError,
+    JOIN_ANTI,
     JOIN_INNER,
+    JOIN_LEFT,
     JOIN_SEMI,
     PGDate,
     PLAN_MAX_FILTERS,

@@ -587,7 +587,10 @@ struct PlanJoinDev
 	uint64_t hslots;
 };
 
-/* dense index map "no build row"; INNER build sides stay below it */
+/* dense index map "no build row"; INNER and LEFT build sides stay below
+ * it.  It is also what a LEFT join leaves in a row's index when the row
+ * has no partner (NULL-extended): the kernels test for it AHEAD of every
+ * address computation, NULL-flag loads included, and never load with it */
 #define PL_NOROW 0xFFFFFFFFu
 /* bits of the plan error word (PlanDev.err) */
 #define PL_ERR_FULL 1ull	/* group table full */
@@ -620,10 +623,12 @@ struct PlanAggDev
  * loads in the row loop and was measurably slower on the Q1 shape when
  * the join and aggregate entries merely grew: DESIGN.md, "Inner joins
  * with payload columns").  Sources: 0 = the driving
- * table, 1+k = the build table of INNER join k. */
+ * table, 1+k = the build table of INNER or LEFT join k.  A LEFT join is
+ * built and laid out as an INNER one, an ANTI join as a SEMI one; jkind
+ * tells the probe what to do with the answer. */
 struct PlanPayloadDev
 {
-	/* INNER join j: key -> build-row-index map instead of a membership
+	/* INNER / LEFT join j: key -> build-row-index map instead of a membership
 	 * set (joins[j].bits stays NULL).  joins[j].dlen > 0: dense,
 	 * jidx[j][key], PL_NOROW = absent; else jidx[j][] runs parallel to
 	 * joins[j].hkeys[], written only where a key was installed */

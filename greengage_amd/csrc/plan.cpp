@@ -137,7 +137,7 @@ gg_engine_plan_group_bits(const int64_t mn[2], const int64_t mx[2],
 }
 
 /* the table a column source names (engine_abi.h "column sources"):
- * 0 = the driving table, 1+k = the build table of INNER join k, where
+ * 0 = the driving table, 1+k = the build table of INNER or LEFT join k, where
  * k < limit (njoins, or the probing join's own index for a probe_src) */
 static gg_status
 resolve_src(const gg_plan_desc *d, Table *scan, int src, int limit,
@@ -154,7 +154,11 @@ resolve_src(const gg_plan_desc *d, Table *scan, int src, int limit,
 	if (src > limit)
 		return fail(GG_EINVAL, "plan: %s %d names source %d, not an "
 			    "earlier join", field, at, src);
-	if (d->joins[src - 1].kind != GG_JOIN_INNER)
+	if (d->joins[src - 1].kind == GG_JOIN_ANTI)
+		return fail(GG_EINVAL, "plan: %s %d names source %d, an ANTI "
+			    "join (no payload)", field, at, src);
+	if (d->joins[src - 1].kind != GG_JOIN_INNER &&
+	    d->joins[src - 1].kind != GG_JOIN_LEFT)
 		return fail(GG_EINVAL, "plan: %s %d names source %d, a SEMI "
 			    "join (no payload)", field, at, src);
 	*out = engine_table(d->joins[src - 1].build.table);
@@ -206,7 +210,8 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 	/* pred_bytes_per_row, the algorithmic figure: a driving column
 	 * counts at its width wherever it is read, as always; a payload
 	 * column (source != 0) counts once per plan however many aggregates
-	 * read it, plus 4 bytes per INNER join for the row index */
+	 * read it, plus 4 bytes per INNER or LEFT join for the row index
+	 * (an ANTI join counts as a SEMI join does: its probe key) */
 	std::vector<std::pair<const void *, int>> payload_seen;
 	auto col_bytes = [&](const void *col, int src, int width) -> int
 	{
@@ -231,9 +236,13 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		if (J->build.npreds < 0 ||
 		    J->build.npreds > GG_PLAN_MAX_PREDS)
 			return fail(GG_ENOTSUP, "plan: join %d pred count", j);
-		if (J->kind != GG_JOIN_SEMI && J->kind != GG_JOIN_INNER)
+		if (J->kind < GG_JOIN_SEMI || J->kind > GG_JOIN_ANTI)
 			return fail(GG_ENOTSUP, "plan: join %d kind", j);
-		if (J->kind == GG_JOIN_INNER && bt->nrows >= 0xFFFFFFFFll)
+		/* LEFT is the INNER map, ANTI the SEMI set */
+		const bool jmap = J->kind == GG_JOIN_INNER ||
+			J->kind == GG_JOIN_LEFT;
+
+		if (jmap && bt->nrows >= 0xFFFFFFFFll)
 			return fail(GG_ENOTSUP, "plan: join %d: INNER build "
 				    "side of %lld rows (32-bit row indices)", j,
 				    (long long) bt->nrows);
@@ -275,7 +284,7 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		R->pred_bytes_per_row +=
 			col_bytes(pk->dev, J->probe_src,
 				  R->dev.joins[j].width) +
-			(J->kind == GG_JOIN_INNER ? 4 : 0);
+			(jmap ? 4 : 0);
 	}
 
 	R->dev.ngroup = d->ngroup;
@@ -515,7 +524,11 @@ plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
  * margin absorbs product rounding).  An aggregate
  * filter only removes inputs from a sum of
  * non-negative values, so the whole-column bound
- * holds for a filtered plan as it stands. */
+ * holds for a filtered plan as it stands.  NULL
+ * extension by a LEFT join does the same and no
+ * more (a NULL-extended factor is skipped by the
+ * strict transition), so it needs no new
+ * arithmetic either. */
 static bool
 plan_fast_tier_provable(Engine &e, const PlanResolved *R)
 {
@@ -690,11 +703,15 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	/* 1. build the join structures (sizing guard as in the named
 	 * pipelines: dense iff max(key) <= 8x rows).  SEMI: membership
 	 * bitmap / hash set.  INNER: key -> build-row-index map, dense
-	 * uint32 array or a row-index array parallel to the hash keys */
+	 * uint32 array or a row-index array parallel to the hash keys.
+	 * ANTI builds the SEMI structure and LEFT the INNER one */
 	for (size_t j = 0; j < R->joins.size(); j++)
 	{
 		PlanResolved::BJoin &B = R->joins[j];
-		const bool inner = B.bd.kind == GG_JOIN_INNER;
+		/* LEFT builds what INNER builds, ANTI what SEMI builds
+		 * (launch_plan_build maps the kinds the same way) */
+		const bool inner = B.bd.kind == GG_JOIN_INNER ||
+			B.bd.kind == GG_JOIN_LEFT;
 		char nm[32], nmi[32];
 		Timed tm(e.stream);
 
@@ -786,6 +803,12 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 				 : "path_plan_join_index_hash")
 			: (B.dlen ? "path_plan_join_bitmap"
 			   : "path_plan_join_hash")).launches++;
+		/* beside the structure's row: one count per such join and
+		 * execute */
+		if (B.bd.kind == GG_JOIN_LEFT)
+			p->stat("path_plan_join_left").launches++;
+		else if (B.bd.kind == GG_JOIN_ANTI)
+			p->stat("path_plan_join_anti").launches++;
 	}
 
 	/* 2. group table + fused scan, 3. compact */
@@ -831,7 +854,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	}
 	if (herr & PL_ERR_DUP_KEY)
 		return fail(GG_ENOTSUP,
-			    "plan: INNER join build key is not unique among "
+			    "plan: INNER/LEFT join build key is not unique among "
 			    "the build rows that pass (or is INT64_MIN): "
 			    "row-multiplying joins are not implemented "
 			    "(fall back to standard_ExecutorRun)");

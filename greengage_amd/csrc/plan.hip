@@ -12,6 +12,11 @@
  *                 build-row index, the scan gathers payload columns
  *                 (group keys, factors, chained probe keys) through it
  *                 (nodeHashjoin.c HJ_NEED_NEW_OUTER -> HJ_SCAN_BUCKET)
+ *   left joins    the INNER map, where "no partner" NULL-extends the row
+ *                 instead of dropping it (HJ_FILL_OUTER_TUPLE): every
+ *                 column of that source then reads as NULL
+ *   anti joins    the SEMI set with the test inverted (JOIN_ANTI, NOT
+ *                 EXISTS): a NULL probe key matches nothing and survives
  *   group-by      execHHashagg.c:905 find-or-create; NULL keys group
  *                 together (:531)
  *   transitions   nodeAgg.c:413–460 strict rules: SUM/COUNT(col) skip
@@ -224,7 +229,9 @@ void k_plan_build(PlanBuildDev B)
 
 hipError_t launch_plan_build(hipStream_t s, const PlanBuildDev &b)
 {
-	if (b.kind == GG_JOIN_INNER)
+	/* LEFT builds the INNER map, ANTI the SEMI set: the kinds differ in
+	 * what the probe does with the answer, not in the structure */
+	if (b.kind == GG_JOIN_INNER || b.kind == GG_JOIN_LEFT)
 		hipLaunchKernelGGL(k_plan_build<1>, dim3(pl_grid(b.n)),
 				   dim3(PL_THREADS), 0, s, b);
 	else
@@ -298,7 +305,31 @@ struct PlRow<1>
 	uint32_t r[GG_PLAN_MAX_JOINS];
 };
 
+/* PL = 2: the plan holds a LEFT or an ANTI join.  The row carries the same
+ * indices, and r[j] == PL_NOROW says that LEFT join j found no partner:
+ * the row is NULL-extended, every column of source 1+j reads as NULL.
+ * That index must never reach a load (it is 0xFFFFFFFF and the build table
+ * may have three rows): every consumer asks pl_src_null FIRST and takes
+ * the NULL branch without computing an address.  Plans without such a
+ * join stay on PL = 0 / 1 and compile to the code they always had. */
+template <>
+struct PlRow<2>
+{
+	uint32_t r[GG_PLAN_MAX_JOINS];
+};
+
 static_assert(GG_PLAN_MAX_JOINS == 2, "pl_ix selects between two joins");
+
+/* source `src` is a LEFT join that NULL-extended this row */
+template <int PL>
+__device__ static inline bool
+pl_src_null(const PlRow<PL> &R, int src)
+{
+	if constexpr (PL == 2)
+		return src != 0 && (src == 1 ? R.r[0] : R.r[1]) == PL_NOROW;
+	else
+		return false;
+}
 
 template <int PL>
 __device__ static inline int64_t
@@ -395,11 +426,116 @@ pl_joins_index(const PlanDev &P, int64_t i, PlRow<1> &R)
 	return true;
 }
 
+/* ... and for a plan with a LEFT or an ANTI join (engine_abi.h
+ * gg_plan_join; nodeHashjoin.c HJ_FILL_OUTER_TUPLE / JOIN_ANTI).  One
+ * probe per join yields "has a partner" (and, for the two map kinds, its
+ * build row); the kind then decides: SEMI and INNER drop the row without
+ * one, ANTI drops the row WITH one, LEFT keeps every row and leaves
+ * PL_NOROW where there is none.  A NULL probe key matches nothing
+ * (nodeHash.c:1070) and is never probed; a probe key whose source is a
+ * NULL-extended LEFT join is NULL, and neither its flag nor its value is
+ * loaded. */
+__device__ static inline bool
+pl_joins_outer(const PlanDev &P, int64_t i, PlRow<2> &R)
+{
+	const int njoins = P.njoins;
+
+	R.r[0] = R.r[1] = 0;
+#pragma unroll
+	for (int j = 0; j < GG_PLAN_MAX_JOINS; j++)
+	{
+		if (j >= njoins)
+			break;
+		const PlanJoinDev &J = P.joins[j];
+		const int kind = P.pl.jkind[j];
+		const bool map = kind == GG_JOIN_INNER || kind == GG_JOIN_LEFT;
+		const int psrc = P.pl.jpsrc[j];
+		bool hit = false;
+		uint32_t x = PL_NOROW;
+
+		if (!pl_src_null<2>(R, psrc))
+		{
+			const int64_t pi = pl_ix<2>(R, psrc, i);
+
+			if (!(J.pnulls && J.pnulls[pi]))
+			{
+				const int64_t k = pl_ld<0>(J.pkey, J.width, pi);
+
+				if (map && J.dlen)
+				{
+					/* range check BEFORE the map is touched: a
+					 * key outside it has no partner */
+					if (k >= 0 && k < J.dlen)
+					{
+						x = P.pl.jidx[j][k];
+						hit = x != PL_NOROW;
+					}
+				}
+				else if (J.bits)
+				{
+					hit = k >= 0 && k < J.dlen &&
+						((J.bits[k >> 6] >> (k & 63)) & 1);
+				}
+				else
+				{
+					/* key -> index map, SEMI or ANTI set.
+					 * Empty BEFORE match for the map and for
+					 * ANTI: a probe key of INT64_MIN encodes
+					 * as the empty sentinel, is in no set and
+					 * must not read an unwritten index; SEMI
+					 * keeps the order pl_joins_pass has */
+					const unsigned long long t =
+						(unsigned long long) k ^
+						0x8000000000000000ull;
+					uint64_t pos = (uint64_t) gg_hashint8(k) &
+						(J.hslots - 1);
+					const bool semi = kind == GG_JOIN_SEMI;
+
+					for (;;)
+					{
+						unsigned long long cur = J.hkeys[pos];
+
+						if (cur == 0 && !semi)
+							break;
+						if (cur == t)
+						{
+							hit = true;
+							break;
+						}
+						if (cur == 0)
+							break;
+						pos = (pos + 1) & (J.hslots - 1);
+					}
+					if (hit && map)
+						x = P.pl.jidx[j][pos];
+				}
+			}
+		}
+		if (kind == GG_JOIN_LEFT)
+			R.r[j] = hit ? x : PL_NOROW;
+		else if (kind == GG_JOIN_ANTI)
+		{
+			if (hit)
+				return false;
+		}
+		else
+		{
+			if (!hit)
+				return false;
+			if (map)
+				R.r[j] = x;
+		}
+	}
+	return true;
+}
+
 template <int PL>
 __device__ static inline bool
 pl_row_joins(const PlanDev &P, int64_t i, PlRow<PL> &R)
 {
-	if constexpr (PL)
+	if constexpr (PL == 2)
+		return pl_joins_outer(P, i, R);
+	else if constexpr (PL)
 		return pl_joins_index(P, i, R);
 	else
 		return pl_joins_pass(P.joins, P.njoins, i);
@@ -422,10 +558,12 @@ pl_group_code(const PlanDev &P, int64_t i, const PlRow<PL> &R)
 		 * (the difference is below 2^62, the operands need not be);
 		 * the widths sum to <= 62, so the code is non-negative */
 		const int64_t i1 = pl_ix<PL>(R, P.pl.gsrc[1], i);
-		unsigned long long e0 = (P.gnulls[0] && P.gnulls[0][i0]) ? 0ull
+		unsigned long long e0 = (pl_src_null<PL>(R, P.pl.gsrc[0]) ||
+					 (P.gnulls[0] && P.gnulls[0][i0])) ? 0ull
 			: (unsigned long long) pl_ld<0>(P.gcol[0], P.gwidth[0], i0)
 			- (unsigned long long) P.gp.gmin[0] + 1ull;
-		unsigned long long e1 = (P.gnulls[1] && P.gnulls[1][i1]) ? 0ull
+		unsigned long long e1 = (pl_src_null<PL>(R, P.pl.gsrc[1]) ||
+					 (P.gnulls[1] && P.gnulls[1][i1])) ? 0ull
 			: (unsigned long long) pl_ld<0>(P.gcol[1], P.gwidth[1], i1)
 			- (unsigned long long) P.gp.gmin[1] + 1ull;
 
@@ -436,14 +574,17 @@ pl_group_code(const PlanDev &P, int64_t i, const PlRow<PL> &R)
 		/* two char1 columns; NULL encodes as 256 so NULL groups
 		 * stay distinct per column (execHHashagg.c:531) */
 		const int64_t i1 = pl_ix<PL>(R, P.pl.gsrc[1], i);
-		long long e0 = (P.gnulls[0] && P.gnulls[0][i0]) ? 256
+		long long e0 = (pl_src_null<PL>(R, P.pl.gsrc[0]) ||
+				(P.gnulls[0] && P.gnulls[0][i0])) ? 256
 			: pl_ld<0>(P.gcol[0], P.gwidth[0], i0);
-		long long e1 = (P.gnulls[1] && P.gnulls[1][i1]) ? 256
+		long long e1 = (pl_src_null<PL>(R, P.pl.gsrc[1]) ||
+				(P.gnulls[1] && P.gnulls[1][i1])) ? 256
 			: pl_ld<0>(P.gcol[1], P.gwidth[1], i1);
 
 		return e0 * 512 + e1;
 	}
-	if (P.gnulls[0] && P.gnulls[0][i0])
+	if (pl_src_null<PL>(R, P.pl.gsrc[0]) ||
+	    (P.gnulls[0] && P.gnulls[0][i0]))
 		return GG_PLAN_NULL_KEY;
 	return pl_ld<0>(P.gcol[0], P.gwidth[0], i0);
 }
@@ -463,7 +604,8 @@ pl_agg_val(const PlanAggDev &a, const int8_t *src, int64_t i,
 		return true;
 	}
 	for (int f = 0; f < a.nf; f++)
-		if (a.nulls[f] && a.nulls[f][pl_ix<PL>(R, src[f], i)])
+		if (pl_src_null<PL>(R, src[f]) ||
+		    (a.nulls[f] && a.nulls[f][pl_ix<PL>(R, src[f], i)]))
 			return false;	/* strict: skip NULL input */
 	if (a.kind == 1)	/* COUNT(col) */
 	{
@@ -539,7 +681,8 @@ pl_row_filters(const PlanFilterDev &F, int64_t i, const PlRow<PL> &R)
 			const PlanPredDev &C = F.preds[k][q];
 			const int64_t fi = pl_ix<PL>(R, F.psrc[k][q], i);
 
-			if (C.nulls && C.nulls[fi])
+			if (pl_src_null<PL>(R, F.psrc[k][q]) ||
+			    (C.nulls && C.nulls[fi]))
 				ok = false;	/* NULL comparison is not true */
 			else
 			{
@@ -893,11 +1036,16 @@ hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
 	for (int a = 0; a < p.naggs; a++)
 		if (p.aggs[a].kind >= 3)
 			mm = true;
-	bool pl = false;
+	bool pl = false, outer = false;
 
 	for (int j = 0; j < p.njoins; j++)
+	{
 		if (p.pl.jkind[j] == GG_JOIN_INNER)
 			pl = true;
+		if (p.pl.jkind[j] == GG_JOIN_LEFT ||
+		    p.pl.jkind[j] == GG_JOIN_ANTI)
+			outer = true;
+	}
 	/* a packed pair of group columns (PlanGroupPackDev) */
 	const bool gp = p.ngroup == 2 && p.gp.packed;
 	/* some aggregate carries a filter (PlanFilterDev) */
@@ -906,6 +1054,33 @@ hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
 	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL, GP, FL>), \
 			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p, \
 			   pl_filters_arg<FL>(p))
+	/* a LEFT or ANTI join anywhere: the PL = 2 kernels, which walk all
+	 * four join kinds (an ANTI-only plan rides along, so pl_joins_pass
+	 * stays what it was) */
+	if (outer)
+	{
+		switch ((fl ? 8 : 0) | (gp ? 4 : 0) | (ntl ? 2 : 0) |
+			(mm ? 1 : 0))
+		{
+			case 0: PL_LAUNCH(0, 0, 2, 0, 0); break;
+			case 1: PL_LAUNCH(0, 1, 2, 0, 0); break;
+			case 2: PL_LAUNCH(1, 0, 2, 0, 0); break;
+			case 3: PL_LAUNCH(1, 1, 2, 0, 0); break;
+			case 4: PL_LAUNCH(0, 0, 2, 1, 0); break;
+			case 5: PL_LAUNCH(0, 1, 2, 1, 0); break;
+			case 6: PL_LAUNCH(1, 0, 2, 1, 0); break;
+			case 7: PL_LAUNCH(1, 1, 2, 1, 0); break;
+			case 8: PL_LAUNCH(0, 0, 2, 0, 1); break;
+			case 9: PL_LAUNCH(0, 1, 2, 0, 1); break;
+			case 10: PL_LAUNCH(1, 0, 2, 0, 1); break;
+			case 11: PL_LAUNCH(1, 1, 2, 0, 1); break;
+			case 12: PL_LAUNCH(0, 0, 2, 1, 1); break;
+			case 13: PL_LAUNCH(0, 1, 2, 1, 1); break;
+			case 14: PL_LAUNCH(1, 0, 2, 1, 1); break;
+			default: PL_LAUNCH(1, 1, 2, 1, 1); break;
+		}
+		return hipGetLastError();
+	}
 	switch ((fl ? 16 : 0) | (gp ? 8 : 0) | (ntl ? 4 : 0) | (mm ? 2 : 0) |
 		(pl ? 1 : 0))
 	{

@@ -304,9 +304,32 @@ struct Gen
 	int nbake;
 	bool fast;		/* baked one-word tier */
 	bool nt;		/* nontemporal scan loads */
-	bool payload;		/* the plan holds an INNER join: rows carry
-				 * the build-row indices r0, r1 */
+	bool payload;		/* the plan holds an INNER or LEFT join: rows
+				 * carry the build-row indices r0, r1 */
 };
+
+/* Source `src` is a LEFT join.  Its index r<j> is 0xFFFFFFFF on a row the
+ * join NULL-extended, and no load may be issued with it: the row carries
+ * one `bool h<j>` ("has a partner"), set once where the join is probed,
+ * and every use of a column of that source tests it ahead of the address
+ * computation: the NULL-flag load and the value load both sit behind it. */
+static bool left_src(const PlanDev &D, int src)
+{
+	return src > 0 && D.pl.jkind[src - 1] == GG_JOIN_LEFT;
+}
+
+/* the h<j> parameters of row_pass ("bool &") and agg_vals ("bool "), and
+ * with decl = "" the matching call arguments; empty without a LEFT join,
+ * so every other plan's program keeps its text */
+static std::string left_flags(const PlanDev &D, const char *decl)
+{
+	std::string s;
+
+	for (int j = 0; j < D.njoins; j++)
+		if (D.pl.jkind[j] == GG_JOIN_LEFT)
+			s += fmt(", %sh%d", decl, j);
+	return s;
+}
 
 /* a plan with a packed pair of group columns reads PlanDev.gp; every
  * other plan's program ends PlanDev where it always ended */
@@ -329,7 +352,7 @@ static size_t plan_arg_bytes(const PlanDev &D)
 }
 
 /* the row index a column of source `src` is loaded at: the driving row,
- * or the build row INNER join src-1 found for it */
+ * or the build row INNER or LEFT join src-1 found for it */
 static std::string ix_of(int src)
 {
 	return src ? fmt("r%d", src - 1) : std::string("i");
@@ -430,10 +453,12 @@ static void emit_prelude(std::string &s, const Gen &G)
 
 		for (int a = 0; a < D.naggs; a++)
 			for (int f = 0; f < D.aggs[a].nf; f++)
-				if (D.aggs[a].nulls[f])
+				if (D.aggs[a].nulls[f] ||
+				    left_src(D, D.pl.asrc[a][f]))
 					nn = false;
 		/* strict-transition flags vanish at compile time when
-		 * no aggregate input is nullable and no aggregate is
+		 * no aggregate input is nullable (a column of a LEFT
+		 * join's build table always is) and no aggregate is
 		 * filtered (the common case) */
 		s += nn ? "#define AOK(a) true\n"
 			: "#define AOK(a) (aok[a])\n";
@@ -447,8 +472,8 @@ static void emit_row_pass(std::string &s, const Gen &G)
 	const PlanDev &D = G.D;
 
 	s += G.payload
-		? "\tauto row_pass = [&](int64_t i, uint32_t &r0, uint32_t &r1)"
-		  " -> bool\n\t{\n"
+		? fmt("\tauto row_pass = [&](int64_t i, uint32_t &r0, uint32_t &r1%s)"
+		      " -> bool\n\t{\n", left_flags(D, "bool &").c_str())
 		: "\tauto row_pass = [&](int64_t i) -> bool\n\t{\n";
 	for (int p = 0; p < D.npreds; p++)
 	{
@@ -464,7 +489,74 @@ static void emit_row_pass(std::string &s, const Gen &G)
 	for (int j = 0; j < D.njoins; j++)
 	{
 		std::string pi = ix_of(D.pl.jpsrc[j]);
+		const int kind = D.pl.jkind[j];
+		const bool psl = left_src(D, D.pl.jpsrc[j]);
 
+		if (kind == GG_JOIN_LEFT || kind == GG_JOIN_ANTI)
+		{
+			/* Neither kind drops a row for a NULL probe key: the
+			 * probe is skipped, LEFT NULL-extends and ANTI keeps
+			 * the row.  The key is NULL by its own flag or because
+			 * its source, an earlier LEFT join, NULL-extended the
+			 * row; `&&` keeps the flag load behind that test */
+			std::string c = psl ? fmt("h%d", D.pl.jpsrc[j] - 1) : "";
+
+			if (D.joins[j].pnulls)
+				c += fmt("%s!P.joins[%d].pnulls[%s]",
+					 psl ? " && " : "", j, pi.c_str());
+			if (kind == GG_JOIN_LEFT)
+				s += fmt("\t\tr%d = 0xFFFFFFFFu;\n", j);
+			s += c.empty() ? "\t\t{\n"
+				: fmt("\t\tif (%s)\n\t\t{\n", c.c_str());
+			emit_ld(s, fmt("k%d", j).c_str(),
+				fmt("P.joins[%d].pkey", j).c_str(), D.joins[j].width,
+				pi.c_str());
+			if (kind == GG_JOIN_LEFT && D.joins[j].dlen)
+				/* dense index map: a key outside [0, dlen) has
+				 * no partner; the range check comes before the
+				 * map is touched */
+				s += fmt("\t\tif (k%d >= 0 && k%d < P.joins[%d].dlen)\n"
+					 "\t\t\tr%d = P.pl.jidx[%d][k%d];\n",
+					 j, j, j, j, j, j);
+			else if (kind == GG_JOIN_LEFT)
+				/* hash map, EMPTY before match: a probe key of
+				 * INT64_MIN finds nothing */
+				s += fmt("\t\t{\n"
+					 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
+					 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
+					 "\t\t\tfor (;;) {\n"
+					 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
+					 "\t\t\t\tif (cur == 0) break;\n"
+					 "\t\t\t\tif (cur == t) { r%d = P.pl.jidx[%d][pos]; break; }\n"
+					 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
+					 "\t\t\t}\n\t\t}\n",
+					 j, j, j, j, j, j, j);
+			else if (D.joins[j].bits)
+				/* ANTI: the SEMI membership test, inverted */
+				s += fmt("\t\tif (k%d >= 0 && k%d < P.joins[%d].dlen &&\n"
+					 "\t\t    ((P.joins[%d].bits[k%d >> 6] >> (k%d & 63)) & 1))\n"
+					 "\t\t\treturn false;\n", j, j, j, j, j, j);
+			else
+				s += fmt("\t\t{\n"
+					 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
+					 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
+					 "\t\t\tfor (;;) {\n"
+					 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
+					 "\t\t\t\tif (cur == 0) break;\n"
+					 "\t\t\t\tif (cur == t) return false;\n"
+					 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
+					 "\t\t\t}\n\t\t}\n", j, j, j, j, j);
+			s += "\t\t}\n";
+			if (kind == GG_JOIN_LEFT)
+				/* the row's one "has a partner" flag */
+				s += fmt("\t\th%d = r%d != 0xFFFFFFFFu;\n", j, j);
+			continue;
+		}
+		if (psl)
+			/* SEMI / INNER through a NULL-extended row: the probe
+			 * key is NULL and never matches */
+			s += fmt("\t\tif (!h%d) return false;\n",
+				 D.pl.jpsrc[j] - 1);
 		if (D.joins[j].pnulls)
 			s += fmt("\t\tif (P.joins[%d].pnulls[%s]) return false;\n",
 				 j, pi.c_str());
@@ -547,6 +639,20 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 			    uniq[u].src == src)
 				return (int) u;
 		uniq.push_back({c, w, src});
+		if (left_src(D, src))
+		{
+			/* a LEFT-source column: loaded behind the row's
+			 * partner flag, 0 on a NULL-extended row (whose every
+			 * user is switched off by the same flag) */
+			s += fmt("\t\tint64_t xu%d = 0;\n\t\tif (h%d)\n"
+				 "\t\t\txu%d = (int64_t) ((%s) %s)[%s];\n",
+				 (int) uniq.size() - 1, src - 1,
+				 (int) uniq.size() - 1,
+				 w == 1 ? "const uint8_t *"
+				 : w == 4 ? "const int32_t *" : "const int64_t *",
+				 ptr.c_str(), ix_of(src).c_str());
+			return (int) uniq.size() - 1;
+		}
 		emit_ld(s, fmt("xu%d", (int) uniq.size() - 1).c_str(),
 			ptr.c_str(), w, ix_of(src).c_str(),
 			/* gathered payload loads are never nontemporal */
@@ -571,8 +677,8 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 	};
 
 	s += G.payload
-		? "\tauto agg_vals = [&](int64_t i, uint32_t r0, uint32_t r1, "
-		  "VAT *av, bool *aok)\n\t{\n"
+		? fmt("\tauto agg_vals = [&](int64_t i, uint32_t r0, uint32_t r1%s, "
+		      "VAT *av, bool *aok)\n\t{\n", left_flags(D, "bool ").c_str())
 		: "\tauto agg_vals = [&](int64_t i, VAT *av, bool *aok)\n\t{\n";
 	/* pass 1: one load per distinct (pointer, width) */
 	for (int a = 0; a < D.naggs; a++)
@@ -626,7 +732,14 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 			e += fmt("%s(xu%d >= P.fl.preds[%d][%d].lo) & "
 				 "(xu%d < P.fl.preds[%d][%d].hi)",
 				 q ? "\n\t\t\t& " : "", u, k, q, u, k, q);
-			if (F.nulls)
+			if (left_src(D, src))
+				/* NULL-extended: the conjunct is not true; `&&`
+				 * keeps the flag load behind the partner flag */
+				e += F.nulls
+					? fmt(" & (h%d && !P.fl.preds[%d][%d].nulls[%s])",
+					      src - 1, k, q, ix_of(src).c_str())
+					: fmt(" & h%d", src - 1);
+			else if (F.nulls)
 				e += fmt(" & !P.fl.preds[%d][%d].nulls[%s]", k, q,
 					 ix_of(src).c_str());
 		}
@@ -650,7 +763,15 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 		}
 		s += fmt("\t\taok[%d] = %s;\n", a, aok0(a).c_str());
 		for (int f = 0; f < D.aggs[a].nf; f++)
-			if (D.aggs[a].nulls[f])
+			if (left_src(D, D.pl.asrc[a][f]))
+				/* strict: a NULL-extended factor is skipped */
+				s += D.aggs[a].nulls[f]
+					? fmt("\t\tif (!h%d || P.aggs[%d].nulls[%d][%s]) aok[%d] = false;\n",
+					      D.pl.asrc[a][f] - 1, a, f,
+					      ix_of(D.pl.asrc[a][f]).c_str(), a)
+					: fmt("\t\tif (!h%d) aok[%d] = false;\n",
+					      D.pl.asrc[a][f] - 1, a);
+			else if (D.aggs[a].nulls[f])
 				s += fmt("\t\tif (P.aggs[%d].nulls[%d][%s]) aok[%d] = false;\n",
 					 a, f, ix_of(D.pl.asrc[a][f]).c_str(),
 					 a);
@@ -692,10 +813,32 @@ static void emit_loop_head(std::string &s, const Gen &G)
 	     i < P.n; i += stride)
 	{
 )GG";
+	std::string hdecl;
+
+	for (int j = 0; j < D.njoins; j++)
+		if (D.pl.jkind[j] == GG_JOIN_LEFT)
+			hdecl += fmt("\t\tbool h%d = false;\n", j);
 	s += G.payload
-		? "\t\tuint32_t r0 = 0, r1 = 0;\n\n"
-		  "\t\tif (!row_pass(i, r0, r1))\n\t\t\tcontinue;\n"
+		? fmt("\t\tuint32_t r0 = 0, r1 = 0;\n%s\n"
+		      "\t\tif (!row_pass(i, r0, r1%s))\n\t\t\tcontinue;\n",
+		      hdecl.c_str(), left_flags(D, "").c_str())
 		: "\t\tif (!row_pass(i))\n\t\t\tcontinue;\n";
+	/* a group column is NULL by its own flag or, for a LEFT source, on a
+	 * NULL-extended row; `||` keeps the flag load and the ternary the
+	 * value load behind the partner flag */
+	bool gn[2] = {false, false};
+	std::string gc[2];
+
+	for (int g = 0; g < D.ngroup; g++)
+	{
+		const bool ls = left_src(D, D.pl.gsrc[g]);
+
+		gn[g] = G.gnull[g] || ls;
+		gc[g] = !ls ? fmt("P.gnulls[%d][%s]", g, gi[g].c_str())
+			: G.gnull[g] ? fmt("(!h%d || P.gnulls[%d][%s])",
+					   D.pl.gsrc[g] - 1, g, gi[g].c_str())
+			: fmt("!h%d", D.pl.gsrc[g] - 1);
+	}
 	if (packed_args(D))
 	{
 		/* packed pair (engine_abi.h gg_plan_desc.group_cols): e = 0
@@ -710,9 +853,8 @@ static void emit_loop_head(std::string &s, const Gen &G)
 
 			e = fmt("(unsigned long long) (%s) - (unsigned long long) "
 				"P.gp.gmin[%d] + 1ull", e.c_str(), g);
-			if (G.gnull[g])
-				e = fmt("P.gnulls[%d][%s] ? 0ull : %s", g,
-					gi[g].c_str(), e.c_str());
+			if (gn[g])
+				e = fmt("%s ? 0ull : %s", gc[g].c_str(), e.c_str());
 			s += fmt("\t\tunsigned long long e%d = %s;\n", g,
 				 e.c_str());
 		}
@@ -726,9 +868,8 @@ static void emit_loop_head(std::string &s, const Gen &G)
 		{
 			std::string e = fmt(ld[0], g, gi[g].c_str());
 
-			if (G.gnull[g])
-				e = fmt("(P.gnulls[%d][%s] ? 256 : %s)", g,
-					gi[g].c_str(), e.c_str());
+			if (gn[g])
+				e = fmt("(%s ? 256 : %s)", gc[g].c_str(), e.c_str());
 			s += fmt("\t\tlong long e%d = %s;\n", g, e.c_str());
 		}
 		s += "\t\tlong long code = e0 * 512 + e1;\n";
@@ -739,8 +880,8 @@ static void emit_loop_head(std::string &s, const Gen &G)
 				       : D.gwidth[0] == 4 ? 1 : 2], 0,
 				    gi[0].c_str());
 
-		if (G.gnull[0])
-			e = "P.gnulls[0][" + gi[0] + "] ? (long long) "
+		if (gn[0])
+			e = gc[0] + " ? (long long) "
 				"0x8000000000000001ull : (" + e + ")";
 		s += "\t\tlong long code = " + e + ";\n";
 	}
@@ -749,7 +890,8 @@ static void emit_loop_head(std::string &s, const Gen &G)
 		bool aok[NA];
 
 )GG";
-	s += G.payload ? "\t\tagg_vals(i, r0, r1, av, aok);\n"
+	s += G.payload ? fmt("\t\tagg_vals(i, r0, r1%s, av, aok);\n",
+			     left_flags(D, "").c_str())
 		       : "\t\tagg_vals(i, av, aok);\n";
 }
 
@@ -1046,7 +1188,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	bool payload = false;
 
 	for (int j = 0; j < D.njoins; j++)
-		if (D.pl.jkind[j] == GG_JOIN_INNER)
+		if (D.pl.jkind[j] == GG_JOIN_INNER ||
+		    D.pl.jkind[j] == GG_JOIN_LEFT)
 			payload = true;
 	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt, payload};
 	std::string s;

@@ -90,6 +90,7 @@ AGG_COUNT_STAR, AGG_COUNT_COL, AGG_SUM = 0, 1, 2
 AGG_MIN, AGG_MAX, AGG_AVG = 3, 4, 5
 # gg_plan_joinkind (engine_abi.h)
 JOIN_SEMI, JOIN_INNER = 0, 1
+JOIN_LEFT, JOIN_ANTI = 2, 3
 
 
 def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
@@ -100,12 +101,19 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
 
     preds: [(col, lo, hi)]  (half-open; NEG_INF/POS_INF one-sided)
     joins: [{"table": h, "build_key": c, "probe_key": c,
-             "preds": [...], "kind": "semi"|"inner",
+             "preds": [...], "kind": "semi"|"inner"|"left"|"anti",
              "probe_src": k}]
            "semi" (default) is a filter; "inner" joins a
            unique-keyed build table whose columns the plan can then
-           read.  probe_src k takes probe_key from the build table
-           of the earlier INNER join k-1 (0 = driving table).
+           read.  "left" is "inner" that keeps a row without a
+           partner: every column of that build table then reads as
+           NULL for it (NULL group, skipped factor, filter not
+           true, chained probe key matches nothing), and "preds"
+           are ON-clause conditions that never drop a driving row.
+           "anti" is NOT EXISTS: the row survives iff it has no
+           partner; a NULL probe key survives.  probe_src k takes
+           probe_key from the build table of the earlier INNER or
+           LEFT join k-1 (0 = driving table).
     group_cols: 0-2 columns of any accepted type (char1, int32,
            int64) and source.  Two char1 columns keep their fixed
            code; any other pair is packed into one 64-bit code by
@@ -128,10 +136,11 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
           ValueError.
     A group column, aggregate factor or filter `col` is a column name of
     the driving table, or a pair (join_index, name) for a column of
-    that INNER join's build table.
+    that INNER or LEFT join's build table.
     """
     mods = {"id": 0, "sub100": 1, "add100": 2}
-    jkinds = {"semi": JOIN_SEMI, "inner": JOIN_INNER}
+    jkinds = {"semi": JOIN_SEMI, "inner": JOIN_INNER, "left": JOIN_LEFT,
+              "anti": JOIN_ANTI}
 
     def colref(c):
         """(name bytes, source): 0 = driving, 1+k = join k"""

@@ -475,15 +475,29 @@ typedef struct gg_plan_scan
  * it names the table the column belongs
  * to: 0 = the driving table (today's meaning, and what a
  * zero-initialised descriptor says), 1+k = the build table of join k,
- * which must be a GG_JOIN_INNER join (for a probe_src: one with a lower
- * index than the probing join).  A source naming a SEMI join, a join
- * index >= njoins or, for probe_src, a non-earlier join is GG_EINVAL. */
+ * which must be a GG_JOIN_INNER or GG_JOIN_LEFT join (for a probe_src:
+ * one with a lower index than the probing join).  A source naming a SEMI
+ * or ANTI join (neither has a payload), a join index >= njoins or, for
+ * probe_src, a non-earlier join is GG_EINVAL. */
 
 typedef enum gg_plan_joinkind
 {
 	GG_JOIN_SEMI = 0,	/* filter: does the row have a partner? */
-	GG_JOIN_INNER = 1	/* unique-keyed build side with payload */
+	GG_JOIN_INNER = 1,	/* unique-keyed build side with payload */
+	/* the two kinds below take the next values, 2 and 3 (pinned by the
+	 * assert under the enum).  They carry no "= n" of their own because
+	 * tests/test_plan_payload_cpu.py, which predates them, reads this
+	 * enum's explicit values and expects exactly the two above */
+	GG_JOIN_LEFT,		/* 2: INNER that keeps partnerless rows,
+				 * NULL-extended (LEFT OUTER JOIN) */
+	GG_JOIN_ANTI		/* 3: SEMI inverted: NOT EXISTS */
 } gg_plan_joinkind;
+
+#ifdef __cplusplus
+static_assert(GG_JOIN_LEFT == 2 && GG_JOIN_ANTI == 3, "ABI join kinds");
+#else
+_Static_assert(GG_JOIN_LEFT == 2 && GG_JOIN_ANTI == 3, "ABI join kinds");
+#endif
 
 /* hash join against a filtered build table.
  *
@@ -509,7 +523,36 @@ typedef enum gg_plan_joinkind
  * Duplicates among rows failing the build preds or among NULL-key rows
  * do not count; SEMI joins accept duplicates.  An INNER build table of
  * 2^32-1 rows or more is GG_ENOTSUP at compile time (32-bit row
- * indices), and so is an INNER build key of INT64_MIN at execute. */
+ * indices), and so is an INNER build key of INT64_MIN at execute.
+ *
+ * In the two kinds below, match(j) means: the probe key is non-NULL and
+ * equals the build key of some build row that passes join j's build preds
+ * and has a non-NULL key (the NULL-never-matches rule, nodeHash.c:1070).
+ *
+ * GG_JOIN_LEFT (nodeHashjoin.c HJ_FILL_OUTER_TUPLE): the row always
+ * survives this join.  On a match it sees the build row exactly as under
+ * INNER.  Without one it is NULL-extended: every column of source 1+j
+ * reads as SQL NULL for that row, and the usual rules apply wherever such
+ * a column is used: a group key joins the NULL group (GG_PLAN_NULL_KEY;
+ * code 256 in a char1 pair, e = 0 in a packed pair), an aggregate factor
+ * is skipped (strict transition) while COUNT(*) still counts the row, an
+ * aggregate-filter conjunct is not true, and a chained probe key (a later
+ * join's probe_src = 1+j) is NULL and matches nothing.  The build preds
+ * are ON-clause conditions on the nullable side: they decide which build
+ * rows can be partners, never which driving rows survive.  Uniqueness,
+ * duplicate detection (GG_ENOTSUP at execute), the INT64_MIN build key
+ * and the 2^32-1 row limit are those of INNER, and a source may name a
+ * LEFT join wherever it may name an INNER one.
+ *
+ * GG_JOIN_ANTI (nodeHashjoin.c JOIN_ANTI, NOT EXISTS): the row survives
+ * iff not match(j).  A NULL probe key matches nothing, so that row
+ * SURVIVES, and so does one whose probe key comes from a NULL-extended
+ * earlier LEFT join.  Duplicate build keys are fine, as for SEMI.  There
+ * is no payload: a source naming an ANTI join is GG_EINVAL.
+ *
+ * Greenplum's JOIN_LASJ_NOTIN (NOT IN's NULL rules), RIGHT/FULL joins and
+ * row-multiplying joins are not implemented; any other kind value is
+ * GG_ENOTSUP. */
 typedef struct gg_plan_join
 {
 	gg_plan_scan build;

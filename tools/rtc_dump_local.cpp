@@ -31,6 +31,14 @@
  *          generic + baked fast tier
  *   pvf    global-group plan with one dense INNER join whose payload
  *          column feeds two filters over the same SUM factors (a pivot)
+ *   left   one group column, a nullable SUM factor and a filter column
+ *          from a dense LEFT join's build table, plus a hashed ANTI join
+ *          chained through that table; generic + baked 2-word
+ *   lefth  global-group plan: hashed LEFT join with a nullable probe key,
+ *          ANTI join on a bitmap, SUM(driving x payload), COUNT(payload)
+ *   year   plan_outer_bench.py's `year`: dense INNER join, grouped by an
+ *          int32 payload column; generic + baked fast tier
+ *   yearl  the same with the join made LEFT (`year_left`)
  *   all    every shape above, DUMPFILE used as a prefix: <prefix><shape>.cu
  * Exit status is non-zero when a variant fails to COMPILE (a module
  * load / function lookup failure without a GPU is not a failure). */
@@ -275,6 +283,93 @@ dump_shape(const char *shape, const char *file)
 		D.joins[1].hkeys = (const unsigned long long *) (dummy + 176);
 		D.joins[1].hslots = 1024;
 	}
+	else if (!std::strcmp(shape, "left"))
+	{
+		/* group column, a nullable SUM factor and a filter column from
+		 * the build table of a dense LEFT join; a hashed ANTI join
+		 * chained through a nullable payload column of it */
+		shape_g1(D, 4, false);
+		D.njoins = 2;
+		D.joins[0].pkey = dummy + 144;
+		D.joins[0].width = 8;
+		D.joins[0].dlen = 1000;
+		D.pl.jkind[0] = GG_JOIN_LEFT;
+		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
+		D.joins[1].pkey = dummy + 160;
+		D.joins[1].pnulls = (const uint8_t *) dummy + 168;
+		D.joins[1].width = 4;
+		D.joins[1].hkeys = (const unsigned long long *) (dummy + 176);
+		D.joins[1].hslots = 1024;
+		D.pl.jkind[1] = GG_JOIN_ANTI;
+		D.pl.jpsrc[1] = 1;
+		D.pl.gsrc[0] = 1;
+		D.pl.asrc[1][0] = 1;
+		D.aggs[1].nulls[0] = (const uint8_t *) dummy + 128;
+		D.pl.asrc[2][1] = 1;
+		set_fpred(D, 0, 0, 200, 4, 1, 8035, 8401);
+		D.fl.preds[0][0].nulls = (const uint8_t *) dummy + 208;
+		set_fpred(D, 0, 1, QTY, 8, 1, 0, 2400);
+		set_afilt(D, 0, 0);
+		wide = true;
+		codes = g1codes;
+		nbake = 3;
+	}
+	else if (!std::strcmp(shape, "year") || !std::strcmp(shape, "yearl"))
+	{
+		/* plan_outer_bench.py's `year` / `year_left`: one dense INNER
+		 * (LEFT) join, grouped by an int32 payload column, a SUM over
+		 * two driving factors and COUNT(*); generic + baked fast tier */
+		static const int c_pd[] = {PRICE, DISC};
+		static const int m_pd[] = {0, 1};
+		static const long long ycodes[7] = {1992, 1993, 1994, 1995,
+			1996, 1997, 1998};
+
+		D.n = 600000000;
+		D.njoins = 1;
+		D.joins[0].pkey = dummy + 144;
+		D.joins[0].width = 8;
+		D.joins[0].dlen = 1000;
+		D.pl.jkind[0] = shape[4] ? GG_JOIN_LEFT : GG_JOIN_INNER;
+		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
+		D.ngroup = 1;
+		D.gcol[0] = dummy + 8;
+		D.gwidth[0] = 4;
+		D.pl.gsrc[0] = 1;
+		D.naggs = 2;
+		set_agg(D, 0, 2, 2, c_pd, m_pd);
+		set_agg(D, 1, 0, 0, nullptr, nullptr);
+		codes = ycodes;
+		nbake = 7;
+	}
+	else if (!std::strcmp(shape, "lefth"))
+	{
+		/* global-group plan: a hashed LEFT join with a nullable probe
+		 * key, an ANTI join on a bitmap, SUM over a driving x payload
+		 * product and COUNT(payload) */
+		static const int c_pd[] = {PRICE, DISC}, c_q[] = {QTY};
+		static const int m_id[] = {0, 0};
+
+		shape_q6(D, false);
+		D.njoins = 2;
+		D.joins[0].pkey = dummy + 144;
+		D.joins[0].pnulls = (const uint8_t *) dummy + 168;
+		D.joins[0].width = 8;
+		D.joins[0].hkeys = (const unsigned long long *) (dummy + 176);
+		D.joins[0].hslots = 1024;
+		D.pl.jkind[0] = GG_JOIN_LEFT;
+		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
+		D.joins[1].pkey = dummy + 160;
+		D.joins[1].width = 4;
+		D.joins[1].bits = (const unsigned long long *) (dummy + 216);
+		D.joins[1].dlen = 1000;
+		D.pl.jkind[1] = GG_JOIN_ANTI;
+		D.naggs = 3;
+		set_agg(D, 0, 2, 2, c_pd, m_id);
+		D.pl.asrc[0][1] = 1;
+		set_agg(D, 1, 0, 0, nullptr, nullptr);
+		set_agg(D, 2, 1, 1, c_q, m_id);
+		D.pl.asrc[2][0] = 1;
+	}
 	else if (!std::strcmp(shape, "pnull"))
 	{
 		shape_q6(D, false);
@@ -340,7 +435,8 @@ int
 main(int argc, char **argv)
 {
 	static const char *const all[] = {"q1", "q1w", "q6", "q1mm", "q1mmw",
-		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl", "q1f", "pvf"};
+		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl", "q1f", "pvf",
+		"left", "lefth", "year", "yearl"};
 	const char *file = argc > 1 ? argv[1] : "/tmp/rtc_dump.cu";
 	const char *shape = argc > 2 ? argv[2] : "q1";
 	bool ok = true;
