@@ -639,6 +639,23 @@ struct PlanPayloadDev
 	int8_t asrc[GG_PLAN_MAX_AGGS][3];	/* source of aggs[a].col[f] */
 };
 
+/* The two things host code asks of a gg_plan_joinkind (held as int or
+ * int8_t in the structs above).  What a kind BUILDS: INNER and LEFT a
+ * key -> build-row-index map, so they are column sources and the row
+ * carries their index; SEMI and ANTI a membership set.  What its probe
+ * DOES with a row that has no partner: LEFT keeps it (NULL-extended), and
+ * ANTI is the same test inverted, it drops the row that has one; neither
+ * drops a row for a NULL probe key. */
+constexpr bool gg_join_builds_map(int kind)
+{
+	return kind == GG_JOIN_INNER || kind == GG_JOIN_LEFT;
+}
+
+constexpr bool gg_join_keeps_unmatched(int kind)
+{
+	return kind == GG_JOIN_LEFT || kind == GG_JOIN_ANTI;
+}
+
 /* Packed two-column group code (engine_abi.h gg_plan_desc.group_cols):
  * code = (e0 << shift) | e1, e_g = 0 for NULL, else v - gmin[g] + 1.
  * Set for every ngroup == 2 plan but the (char1, char1) pair, which

@@ -157,8 +157,7 @@ resolve_src(const gg_plan_desc *d, Table *scan, int src, int limit,
 	if (d->joins[src - 1].kind == GG_JOIN_ANTI)
 		return fail(GG_EINVAL, "plan: %s %d names source %d, an ANTI "
 			    "join (no payload)", field, at, src);
-	if (d->joins[src - 1].kind != GG_JOIN_INNER &&
-	    d->joins[src - 1].kind != GG_JOIN_LEFT)
+	if (!gg_join_builds_map(d->joins[src - 1].kind))
 		return fail(GG_EINVAL, "plan: %s %d names source %d, a SEMI "
 			    "join (no payload)", field, at, src);
 	*out = engine_table(d->joins[src - 1].build.table);
@@ -239,8 +238,7 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 		if (J->kind < GG_JOIN_SEMI || J->kind > GG_JOIN_ANTI)
 			return fail(GG_ENOTSUP, "plan: join %d kind", j);
 		/* LEFT is the INNER map, ANTI the SEMI set */
-		const bool jmap = J->kind == GG_JOIN_INNER ||
-			J->kind == GG_JOIN_LEFT;
+		const bool jmap = gg_join_builds_map(J->kind);
 
 		if (jmap && bt->nrows >= 0xFFFFFFFFll)
 			return fail(GG_ENOTSUP, "plan: join %d: INNER build "
@@ -674,44 +672,33 @@ plan_group_pack(Engine &e, Pipeline *p, PlanResolved *R)
 	return GG_OK;
 }
 
-gg_status
-exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
+/* ---- exec_plan's stages, in the order it runs them.  They share the
+ * plan R (R->dev.err is the kernels' error word), the 8-byte device
+ * counter ctr, and the compacted result: rows of (code, naggs x (lo, hi)),
+ * `dout` on the device and `rows` on the host ---- */
+
+/* u64 words per compacted row */
+static int
+plan_rowsz(const PlanResolved *R)
 {
-	Engine &e = engine();
-	PlanResolved *R = (PlanResolved *) p->plan.get();
-	int nseg = e.cfg.n_segments;
+	return 1 + 2 * R->dev.naggs;
+}
 
-	if (!R)
-		return fail(GG_ESTATE, "not a compiled plan");
-	unsigned long long *ctr = (unsigned long long *) p->sget("ctr", 8);
-
-	if (!ctr)
-		return fail(GG_ENOMEM, "plan scratch");
-
-	/* the kernels' error word: the INNER builds report duplicate keys
-	 * in it, so it is cleared ahead of them, not just before the scan */
-	unsigned long long *derr = (unsigned long long *)
-		p->sget("plan.err", 8);
-
-	if (!derr)
-		return fail(GG_ENOMEM, "plan scratch");
-	R->dev.err = derr;
-	GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
-	if (R->dev.gp.packed)
-		GG_TRY(plan_group_pack(e, p, R));
-
-	/* 1. build the join structures (sizing guard as in the named
-	 * pipelines: dense iff max(key) <= 8x rows).  SEMI: membership
-	 * bitmap / hash set.  INNER: key -> build-row-index map, dense
-	 * uint32 array or a row-index array parallel to the hash keys.
-	 * ANTI builds the SEMI structure and LEFT the INNER one */
+/* 1. build the join structures (sizing guard as in the named
+ * pipelines: dense iff max(key) <= 8x rows).  SEMI: membership
+ * bitmap / hash set.  INNER: key -> build-row-index map, dense
+ * uint32 array or a row-index array parallel to the hash keys.
+ * ANTI builds the SEMI structure and LEFT the INNER one */
+static gg_status
+plan_build_joins(Engine &e, Pipeline *p, PlanResolved *R,
+		 unsigned long long *ctr)
+{
 	for (size_t j = 0; j < R->joins.size(); j++)
 	{
 		PlanResolved::BJoin &B = R->joins[j];
 		/* LEFT builds what INNER builds, ANTI what SEMI builds
 		 * (launch_plan_build maps the kinds the same way) */
-		const bool inner = B.bd.kind == GG_JOIN_INNER ||
-			B.bd.kind == GG_JOIN_LEFT;
+		const bool inner = gg_join_builds_map(B.bd.kind);
 		char nm[32], nmi[32];
 		Timed tm(e.stream);
 
@@ -730,7 +717,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			B.hslots = next_pow2_pl(2 * (uint64_t) B.bd.n + 2);
 		std::snprintf(nm, sizeof(nm), "plan.j%zu", j);
 		std::snprintf(nmi, sizeof(nmi), "plan.j%zu.idx", j);
-		B.bd.err = derr;
+		B.bd.err = R->dev.err;
 		B.bd.idx = nullptr;
 		if (B.dlen && inner)
 		{
@@ -810,13 +797,23 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		else if (B.bd.kind == GG_JOIN_ANTI)
 			p->stat("path_plan_join_anti").launches++;
 	}
+	return GG_OK;
+}
 
-	/* 2. group table + fused scan, 3. compact */
+/* 2. group table + fused scan, 3. compact: leaves the segment's groups in
+ * *dout_p and, copied to the host, in `rows`.  The first execute compiles the
+ * plan's generated kernel; a baked kernel that misses is dropped and the
+ * execute redone on the generic one */
+static gg_status
+plan_scan_groups(Engine &e, Pipeline *p, PlanResolved *R,
+		 unsigned long long *ctr, unsigned long long **dout_p,
+		 std::vector<unsigned long long> &rows)
+{
 	uint64_t nslots = R->dev.ngroup == 0 ? 1
 		: (R->dev.ngroup == 2 ? 1 << 19 : PL_NSLOTS);
 	int naggs = R->dev.naggs;
 	uint64_t cap = nslots;
-	int rowsz = 1 + 2 * naggs;
+	int rowsz = plan_rowsz(R);
 	unsigned long long *tkeys = (unsigned long long *)
 		p->sget("plan.tkeys", nslots * 8);
 	unsigned long long *tvals = (unsigned long long *)
@@ -866,7 +863,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		 * generic kernel */
 		R->rtc_baked.reset();
 		p->stat("path_plan_bake_miss").launches++;
-		GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
+		GG_HIP(hipMemsetAsync(R->dev.err, 0, 8, e.stream));
 		GG_TRY(plan_reset_table(e.stream, R->dev));
 		GG_TRY(plan_scan_compact(e, p, R, R->rtc, nullptr, dout, ctr,
 					 &herr));
@@ -880,149 +877,166 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	if (ng > cap)
 		return fail(GG_ESTATE, "plan compact overflow");
 
-	std::vector<unsigned long long> rows((size_t) ng * rowsz);
-
+	rows.resize((size_t) ng * rowsz);
 	if (ng)
 		GG_HIP(hipMemcpy(rows.data(), dout, rows.size() * 8,
 				 hipMemcpyDeviceToHost));
+	*dout_p = dout;
+	return GG_OK;
+}
 
-	/* 4. combine partial states across segments (2-stage agg:
-	 * exact partials + one combine) */
-	if (nseg > 1)
+/* 4. combine partial states across segments (2-stage agg: exact partials
+ * + one combine); `rows` becomes the merged groups, ordered by code */
+static gg_status
+plan_combine_segments(Engine &e, Pipeline *p, const PlanResolved *R,
+		      const unsigned long long *dout,
+		      std::vector<unsigned long long> &rows)
+{
+	const int nseg = e.cfg.n_segments, naggs = R->dev.naggs;
+	const int rowsz = plan_rowsz(R);
+	unsigned long long ng = rows.size() / rowsz;
+
+	if (!comm_ready())
+		return fail(GG_ESTATE,
+			    "multi-segment plan without comm");
+	/* max group count, then padded allgather of rows */
+	std::vector<unsigned long long> cnts(nseg);
+	unsigned long long *g = (unsigned long long *)
+		p->sget("plan.cntg", (1 + (size_t) nseg) * 8);
+
+	if (!g)
+		return fail(GG_ENOMEM, "plan comm scratch");
+	GG_HIP(hipMemcpy(g, &ng, 8, hipMemcpyHostToDevice));
+	GG_TRY(comm_allgather_u64(g, g + 1, 1));
+	GG_HIP(hipMemcpy(cnts.data(), g + 1, (size_t) nseg * 8,
+			 hipMemcpyDeviceToHost));
+	uint64_t mx = 0;
+
+	for (int r = 0; r < nseg; r++)
+		mx = std::max(mx, (uint64_t) cnts[r]);
+	size_t per = (size_t) mx * rowsz;
+
+	if (per)
 	{
-		if (!comm_ready())
-			return fail(GG_ESTATE,
-				    "multi-segment plan without comm");
-		/* max group count, then padded allgather of rows */
-		std::vector<unsigned long long> cnts(nseg);
-		unsigned long long *g = (unsigned long long *)
-			p->sget("plan.cntg", (1 + (size_t) nseg) * 8);
+		unsigned long long *ag = (unsigned long long *)
+			p->sget("plan.allg",
+				(per + per * (size_t) nseg) * 8);
 
-		if (!g)
-			return fail(GG_ENOMEM, "plan comm scratch");
-		GG_HIP(hipMemcpy(g, &ng, 8, hipMemcpyHostToDevice));
-		GG_TRY(comm_allgather_u64(g, g + 1, 1));
-		GG_HIP(hipMemcpy(cnts.data(), g + 1, (size_t) nseg * 8,
+		if (!ag)
+			return fail(GG_ENOMEM, "plan allgather");
+		GG_HIP(hipMemsetAsync(ag, 0, per * 8, e.stream));
+		if (ng)
+			GG_HIP(hipMemcpyAsync(ag, dout,
+					      (size_t) ng * rowsz * 8,
+					      hipMemcpyDeviceToDevice,
+					      e.stream));
+		GG_HIP(hipStreamSynchronize(e.stream));
+		GG_TRY(comm_allgather_u64(ag, ag + per, per));
+		std::vector<unsigned long long> all(per *
+						    (size_t) nseg);
+
+		GG_HIP(hipMemcpy(all.data(), ag + per,
+				 all.size() * 8,
 				 hipMemcpyDeviceToHost));
-		uint64_t mx = 0;
+
+		std::map<long long,
+			 std::vector<i128>> merged;
 
 		for (int r = 0; r < nseg; r++)
-			mx = std::max(mx, (uint64_t) cnts[r]);
-		size_t per = (size_t) mx * rowsz;
-
-		if (per)
-		{
-			unsigned long long *ag = (unsigned long long *)
-				p->sget("plan.allg",
-					(per + per * (size_t) nseg) * 8);
-
-			if (!ag)
-				return fail(GG_ENOMEM, "plan allgather");
-			GG_HIP(hipMemsetAsync(ag, 0, per * 8, e.stream));
-			if (ng)
-				GG_HIP(hipMemcpyAsync(ag, dout,
-						      (size_t) ng * rowsz * 8,
-						      hipMemcpyDeviceToDevice,
-						      e.stream));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(comm_allgather_u64(ag, ag + per, per));
-			std::vector<unsigned long long> all(per *
-							    (size_t) nseg);
-
-			GG_HIP(hipMemcpy(all.data(), ag + per,
-					 all.size() * 8,
-					 hipMemcpyDeviceToHost));
-
-			std::map<long long,
-				 std::vector<i128>> merged;
-
-			for (int r = 0; r < nseg; r++)
-				for (uint64_t i = 0; i < cnts[r]; i++)
-				{
-					const unsigned long long *row =
-						&all[per * (size_t) r +
-						     i * rowsz];
-					auto &acc = merged[(long long)
-							   row[0]];
-
-					if (acc.empty())
-						acc.assign(naggs, 0);
-					for (int a = 0; a < naggs; a++)
-					{
-						i128 v = ((i128) (int64_t)
-							  row[2 + 2 * a] << 64) |
-							(i128) row[1 + 2 * a];
-
-						/* encoded MIN/MAX words merge by
-						 * unsigned max (0 = no input),
-						 * everything else by addition */
-						if (R->dev.aggs[a].kind >= 3)
-							acc[a] = std::max(acc[a], v);
-						else
-							acc[a] += v;
-					}
-				}
-			rows.clear();
-			for (auto &kv : merged)
+			for (uint64_t i = 0; i < cnts[r]; i++)
 			{
-				rows.push_back((unsigned long long)
-					       kv.first);
+				const unsigned long long *row =
+					&all[per * (size_t) r +
+					     i * rowsz];
+				auto &acc = merged[(long long)
+						   row[0]];
+
+				if (acc.empty())
+					acc.assign(naggs, 0);
 				for (int a = 0; a < naggs; a++)
 				{
-					rows.push_back((unsigned long long)
-						       (uint64_t)
-						       kv.second[a]);
-					rows.push_back((unsigned long long)
-						       (uint64_t)
-						       (kv.second[a] >> 64));
+					i128 v = ((i128) (int64_t)
+						  row[2 + 2 * a] << 64) |
+						(i128) row[1 + 2 * a];
+
+					/* encoded MIN/MAX words merge by
+					 * unsigned max (0 = no input),
+					 * everything else by addition */
+					if (R->dev.aggs[a].kind >= 3)
+						acc[a] = std::max(acc[a], v);
+					else
+						acc[a] += v;
 				}
 			}
-			ng = rows.size() / rowsz;
+		rows.clear();
+		for (auto &kv : merged)
+		{
+			rows.push_back((unsigned long long)
+				       kv.first);
+			for (int a = 0; a < naggs; a++)
+			{
+				rows.push_back((unsigned long long)
+					       (uint64_t)
+					       kv.second[a]);
+				rows.push_back((unsigned long long)
+					       (uint64_t)
+					       (kv.second[a] >> 64));
+			}
 		}
 	}
+	return GG_OK;
+}
 
-	/* 5. sort by decoded keys and materialize the arena */
+/* the group keys a code stands for (a NULL key is GG_PLAN_NULL_KEY) */
+static void
+plan_keys_of(const PlanDev &D, long long code, int64_t *k0, int64_t *k1)
+{
+	if (D.gp.packed)
+	{
+		/* (e0 << shift) | e1; e = 0 is NULL, else the
+		 * value's offset from the column minimum, plus 1 */
+		const PlanGroupPackDev &G = D.gp;
+		uint64_t e0 = (uint64_t) code >> G.shift;
+		uint64_t e1 = (uint64_t) code & ((1ull << G.shift) - 1);
+
+		*k0 = e0 ? (int64_t) ((uint64_t) G.gmin[0] + e0 - 1)
+			: GG_PLAN_NULL_KEY;
+		*k1 = e1 ? (int64_t) ((uint64_t) G.gmin[1] + e1 - 1)
+			: GG_PLAN_NULL_KEY;
+	}
+	else if (D.ngroup == 2)
+	{
+		long long e0 = code / 512, e1 = code % 512;
+
+		*k0 = e0 == 256 ? GG_PLAN_NULL_KEY : e0;
+		*k1 = e1 == 256 ? GG_PLAN_NULL_KEY : e1;
+	}
+	else
+	{
+		*k0 = code;
+		*k1 = 0;
+	}
+}
+
+/* 5. sort by decoded keys and materialize the arena */
+static gg_status
+plan_write_arena(const PlanResolved *R,
+		 const std::vector<unsigned long long> &rows, void *arena,
+		 size_t bytes, size_t *written)
+{
+	const int rowsz = plan_rowsz(R);
+	const size_t ng = rows.size() / rowsz;
 	std::vector<size_t> order(ng);
 
 	for (size_t i = 0; i < ng; i++)
 		order[i] = i;
-	auto keys_of = [&](size_t i, int64_t *k0, int64_t *k1)
-	{
-		long long code = (long long) rows[i * rowsz];
-
-		if (R->dev.gp.packed)
-		{
-			/* (e0 << shift) | e1; e = 0 is NULL, else the
-			 * value's offset from the column minimum, plus 1 */
-			const PlanGroupPackDev &G = R->dev.gp;
-			uint64_t e0 = (uint64_t) code >> G.shift;
-			uint64_t e1 = (uint64_t) code & ((1ull << G.shift) - 1);
-
-			*k0 = e0 ? (int64_t) ((uint64_t) G.gmin[0] + e0 - 1)
-				: GG_PLAN_NULL_KEY;
-			*k1 = e1 ? (int64_t) ((uint64_t) G.gmin[1] + e1 - 1)
-				: GG_PLAN_NULL_KEY;
-		}
-		else if (R->dev.ngroup == 2)
-		{
-			long long e0 = code / 512, e1 = code % 512;
-
-			*k0 = e0 == 256 ? GG_PLAN_NULL_KEY : e0;
-			*k1 = e1 == 256 ? GG_PLAN_NULL_KEY : e1;
-		}
-		else
-		{
-			*k0 = code;
-			*k1 = 0;
-		}
-	};
 	std::sort(order.begin(), order.end(),
 		  [&](size_t a, size_t b)
 	{
 		int64_t a0, a1, b0, b1;
 
-		keys_of(a, &a0, &a1);
-		keys_of(b, &b0, &b1);
+		plan_keys_of(R->dev, (long long) rows[a * rowsz], &a0, &a1);
+		plan_keys_of(R->dev, (long long) rows[b * rowsz], &b0, &b1);
 		return a0 != b0 ? a0 < b0 : a1 < b1;
 	});
 
@@ -1045,7 +1059,8 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			size_t i = order[oi];
 			int64_t k0, k1;
 
-			keys_of(i, &k0, &k1);
+			plan_keys_of(R->dev, (long long) rows[i * rowsz], &k0,
+				     &k1);
 			std::memcpy(w, &k0, 8);
 			std::memcpy(w + 8, &k1, 8);
 			w += 16;
@@ -1081,39 +1096,81 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		}
 	}
 	*written = need;
+	return GG_OK;
+}
 
-	/* second-stage bake: with the group set observed (and exact —
-	 * registered tables are immutable), recompile the RTC kernel
-	 * with the codes as a constexpr compare chain so later
-	 * executes of this plan skip key probing entirely.  Gated on a
-	 * small group count (register/LDS budget) and on the first
-	 * RTC compile having succeeded. */
+/* second-stage bake: with the group set observed (and exact —
+ * registered tables are immutable), recompile the RTC kernel
+ * with the codes as a constexpr compare chain so later
+ * executes of this plan skip key probing entirely.  Gated on a
+ * small group count (register/LDS budget) and on the first
+ * RTC compile having succeeded. */
+static void
+plan_bake(Engine &e, Pipeline *p, PlanResolved *R,
+	  const std::vector<unsigned long long> &rows)
+{
+	const int rowsz = plan_rowsz(R);
+	const size_t ng = rows.size() / rowsz;
+	int bake_max = 8;
+	const char *bm = getenv("GG_PLAN_BAKE");
+
+	if (bm && bm[0] == '0')
+		bake_max = 0;
+	if (!R->bake_tried && R->rtc && R->dev.ngroup > 0 &&
+	    ng > 0 && (int64_t) ng <= bake_max)
 	{
-		int bake_max = 8;
-		const char *bm = getenv("GG_PLAN_BAKE");
+		std::vector<long long> codes(ng);
 
-		if (bm && bm[0] == '0')
-			bake_max = 0;
-		if (!R->bake_tried && R->rtc && R->dev.ngroup > 0 &&
-		    ng > 0 && (int64_t) ng <= bake_max)
-		{
-			std::vector<long long> codes(ng);
+		for (size_t i = 0; i < ng; i++)
+			codes[i] = (long long) rows[i * rowsz];
 
-			for (size_t i = 0; i < ng; i++)
-				codes[i] = (long long) rows[i * rowsz];
+		bool fastok = plan_fast_tier_provable(e, R);
+		gg_status rs = plan_rtc_compile(
+			R->dev, R->dev.gnulls[0] != nullptr,
+			R->dev.gnulls[1] != nullptr, &R->rtc_baked,
+			codes.data(), (int) ng, fastok);
 
-			bool fastok = plan_fast_tier_provable(e, R);
-			gg_status rs = plan_rtc_compile(
-				R->dev, R->dev.gnulls[0] != nullptr,
-				R->dev.gnulls[1] != nullptr, &R->rtc_baked,
-				codes.data(), (int) ng, fastok);
-
-			R->bake_tried = true;
-			if (rs == GG_OK)
-				p->stat(fastok ? "path_plan_rtc_baked_fast"
-					: "path_plan_rtc_baked").launches++;
-		}
+		R->bake_tried = true;
+		if (rs == GG_OK)
+			p->stat(fastok ? "path_plan_rtc_baked_fast"
+				: "path_plan_rtc_baked").launches++;
 	}
+}
+
+gg_status
+exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
+{
+	Engine &e = engine();
+	PlanResolved *R = (PlanResolved *) p->plan.get();
+
+	if (!R)
+		return fail(GG_ESTATE, "not a compiled plan");
+	unsigned long long *ctr = (unsigned long long *) p->sget("ctr", 8);
+
+	if (!ctr)
+		return fail(GG_ENOMEM, "plan scratch");
+
+	/* the kernels' error word: the INNER builds report duplicate keys
+	 * in it, so it is cleared ahead of them, not just before the scan */
+	unsigned long long *derr = (unsigned long long *)
+		p->sget("plan.err", 8);
+
+	if (!derr)
+		return fail(GG_ENOMEM, "plan scratch");
+	R->dev.err = derr;
+	GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
+	if (R->dev.gp.packed)
+		GG_TRY(plan_group_pack(e, p, R));
+
+	unsigned long long *dout = nullptr;
+	std::vector<unsigned long long> rows;
+
+	GG_TRY(plan_build_joins(e, p, R, ctr));
+	GG_TRY(plan_scan_groups(e, p, R, ctr, &dout, rows));
+	if (e.cfg.n_segments > 1)
+		GG_TRY(plan_combine_segments(e, p, R, dout, rows));
+	GG_TRY(plan_write_arena(R, rows, arena, bytes, written));
+	plan_bake(e, p, R, rows);
 	return GG_OK;
 }
 

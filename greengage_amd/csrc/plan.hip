@@ -39,7 +39,10 @@
  * the named pipelines.
  */
 #include <hip/hip_runtime.h>
+#include <algorithm>
+#include <array>
 #include <cstdlib>
+#include <utility>
 
 #include "../../include/gg_pg_hash.h"
 #include "engine_internal.h"
@@ -231,7 +234,7 @@ hipError_t launch_plan_build(hipStream_t s, const PlanBuildDev &b)
 {
 	/* LEFT builds the INNER map, ANTI the SEMI set: the kinds differ in
 	 * what the probe does with the answer, not in the structure */
-	if (b.kind == GG_JOIN_INNER || b.kind == GG_JOIN_LEFT)
+	if (gg_join_builds_map(b.kind))
 		hipLaunchKernelGGL(k_plan_build<1>, dim3(pl_grid(b.n)),
 				   dim3(PL_THREADS), 0, s, b);
 	else
@@ -1027,97 +1030,84 @@ static PlFilters<FL> pl_filters_arg(const PlanDev &p)
 	return F;
 }
 
+/* The host launcher of one k_plan_scan_agg instantiation, and the table of
+ * all 48.  Entry i holds the flags pl_decode(i) gives: PL in {0, 1, 2} is
+ * the lowest digit, above it one bit each for MM, NT, GP and FL.  The table
+ * is built from the index sequence alone, and pl_encode is the inverse
+ * launch_plan_scan_agg indexes it by; the static_asserts below pin the pair
+ * at every flag, so a wrong mapping fails the build. */
+template <int NT, int MM, int PL, int GP, int FL>
+static void pl_launch(hipStream_t s, const PlanDev &p)
+{
+	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL, GP, FL>),
+			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p,
+			   pl_filters_arg<FL>(p));
+}
+
+typedef void (*PlLaunchFn)(hipStream_t, const PlanDev &);
+struct PlFlags
+{
+	int nt, mm, pl, gp, fl;
+};
+static constexpr int PL_NKERNELS = 2 * 2 * 3 * 2 * 2;
+
+static constexpr PlFlags pl_decode(int i)
+{
+	return {i / 6 % 2, i / 3 % 2, i % 3, i / 12 % 2, i / 24};
+}
+
+static constexpr int pl_encode(bool nt, bool mm, int pl, bool gp, bool fl)
+{
+	return pl + 3 * (mm + 2 * (nt + 2 * (gp + 2 * fl)));
+}
+
+template <int... I>
+static constexpr std::array<PlLaunchFn, sizeof...(I)>
+pl_table(std::integer_sequence<int, I...>)
+{
+	return {{&pl_launch<pl_decode(I).nt, pl_decode(I).mm, pl_decode(I).pl,
+			    pl_decode(I).gp, pl_decode(I).fl>...}};
+}
+
+static constexpr auto PL_TABLE =
+	pl_table(std::make_integer_sequence<int, PL_NKERNELS>{});
+
+/* the entry pl_encode names for these flags launches exactly their kernel */
+template <int NT, int MM, int PL, int GP, int FL>
+static constexpr bool pl_pinned()
+{
+	return PL_TABLE[pl_encode(NT, MM, PL, GP, FL)] ==
+		&pl_launch<NT, MM, PL, GP, FL>;
+}
+
+static_assert(pl_pinned<0, 0, 0, 0, 0>() && pl_pinned<1, 1, 2, 1, 1>() &&
+	      pl_encode(1, 1, 2, 1, 1) == PL_NKERNELS - 1 &&
+	      pl_pinned<1, 0, 0, 0, 0>() && pl_pinned<0, 1, 0, 0, 0>() &&
+	      pl_pinned<0, 0, 1, 0, 0>() && pl_pinned<0, 0, 2, 0, 0>() &&
+	      pl_pinned<0, 0, 0, 1, 0>() && pl_pinned<0, 0, 0, 0, 1>(),
+	      "k_plan_scan_agg launcher table: decode and encode disagree");
+
 hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
 {
 	const char *nt = getenv("GG_PLAN_NT");
-	bool ntl = nt && nt[0] == '1';
 	bool mm = false;
+	/* 1: the row carries build-row indices (an INNER join); 2: a LEFT or
+	 * ANTI join anywhere, the kernels that walk all four join kinds (an
+	 * ANTI-only plan rides along, so pl_joins_pass stays what it was).
+	 * 2 wins over 1 */
+	int pl = 0;
 
 	for (int a = 0; a < p.naggs; a++)
 		if (p.aggs[a].kind >= 3)
 			mm = true;
-	bool pl = false, outer = false;
-
 	for (int j = 0; j < p.njoins; j++)
-	{
-		if (p.pl.jkind[j] == GG_JOIN_INNER)
-			pl = true;
-		if (p.pl.jkind[j] == GG_JOIN_LEFT ||
-		    p.pl.jkind[j] == GG_JOIN_ANTI)
-			outer = true;
-	}
-	/* a packed pair of group columns (PlanGroupPackDev) */
-	const bool gp = p.ngroup == 2 && p.gp.packed;
-	/* some aggregate carries a filter (PlanFilterDev) */
-	const bool fl = p.fl.used != 0;
-#define PL_LAUNCH(NT, MM, PL, GP, FL) \
-	hipLaunchKernelGGL((k_plan_scan_agg<NT, MM, PL, GP, FL>), \
-			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p, \
-			   pl_filters_arg<FL>(p))
-	/* a LEFT or ANTI join anywhere: the PL = 2 kernels, which walk all
-	 * four join kinds (an ANTI-only plan rides along, so pl_joins_pass
-	 * stays what it was) */
-	if (outer)
-	{
-		switch ((fl ? 8 : 0) | (gp ? 4 : 0) | (ntl ? 2 : 0) |
-			(mm ? 1 : 0))
-		{
-			case 0: PL_LAUNCH(0, 0, 2, 0, 0); break;
-			case 1: PL_LAUNCH(0, 1, 2, 0, 0); break;
-			case 2: PL_LAUNCH(1, 0, 2, 0, 0); break;
-			case 3: PL_LAUNCH(1, 1, 2, 0, 0); break;
-			case 4: PL_LAUNCH(0, 0, 2, 1, 0); break;
-			case 5: PL_LAUNCH(0, 1, 2, 1, 0); break;
-			case 6: PL_LAUNCH(1, 0, 2, 1, 0); break;
-			case 7: PL_LAUNCH(1, 1, 2, 1, 0); break;
-			case 8: PL_LAUNCH(0, 0, 2, 0, 1); break;
-			case 9: PL_LAUNCH(0, 1, 2, 0, 1); break;
-			case 10: PL_LAUNCH(1, 0, 2, 0, 1); break;
-			case 11: PL_LAUNCH(1, 1, 2, 0, 1); break;
-			case 12: PL_LAUNCH(0, 0, 2, 1, 1); break;
-			case 13: PL_LAUNCH(0, 1, 2, 1, 1); break;
-			case 14: PL_LAUNCH(1, 0, 2, 1, 1); break;
-			default: PL_LAUNCH(1, 1, 2, 1, 1); break;
-		}
-		return hipGetLastError();
-	}
-	switch ((fl ? 16 : 0) | (gp ? 8 : 0) | (ntl ? 4 : 0) | (mm ? 2 : 0) |
-		(pl ? 1 : 0))
-	{
-		case 0: PL_LAUNCH(0, 0, 0, 0, 0); break;
-		case 1: PL_LAUNCH(0, 0, 1, 0, 0); break;
-		case 2: PL_LAUNCH(0, 1, 0, 0, 0); break;
-		case 3: PL_LAUNCH(0, 1, 1, 0, 0); break;
-		case 4: PL_LAUNCH(1, 0, 0, 0, 0); break;
-		case 5: PL_LAUNCH(1, 0, 1, 0, 0); break;
-		case 6: PL_LAUNCH(1, 1, 0, 0, 0); break;
-		case 7: PL_LAUNCH(1, 1, 1, 0, 0); break;
-		case 8: PL_LAUNCH(0, 0, 0, 1, 0); break;
-		case 9: PL_LAUNCH(0, 0, 1, 1, 0); break;
-		case 10: PL_LAUNCH(0, 1, 0, 1, 0); break;
-		case 11: PL_LAUNCH(0, 1, 1, 1, 0); break;
-		case 12: PL_LAUNCH(1, 0, 0, 1, 0); break;
-		case 13: PL_LAUNCH(1, 0, 1, 1, 0); break;
-		case 14: PL_LAUNCH(1, 1, 0, 1, 0); break;
-		case 15: PL_LAUNCH(1, 1, 1, 1, 0); break;
-		case 16: PL_LAUNCH(0, 0, 0, 0, 1); break;
-		case 17: PL_LAUNCH(0, 0, 1, 0, 1); break;
-		case 18: PL_LAUNCH(0, 1, 0, 0, 1); break;
-		case 19: PL_LAUNCH(0, 1, 1, 0, 1); break;
-		case 20: PL_LAUNCH(1, 0, 0, 0, 1); break;
-		case 21: PL_LAUNCH(1, 0, 1, 0, 1); break;
-		case 22: PL_LAUNCH(1, 1, 0, 0, 1); break;
-		case 23: PL_LAUNCH(1, 1, 1, 0, 1); break;
-		case 24: PL_LAUNCH(0, 0, 0, 1, 1); break;
-		case 25: PL_LAUNCH(0, 0, 1, 1, 1); break;
-		case 26: PL_LAUNCH(0, 1, 0, 1, 1); break;
-		case 27: PL_LAUNCH(0, 1, 1, 1, 1); break;
-		case 28: PL_LAUNCH(1, 0, 0, 1, 1); break;
-		case 29: PL_LAUNCH(1, 0, 1, 1, 1); break;
-		case 30: PL_LAUNCH(1, 1, 0, 1, 1); break;
-		default: PL_LAUNCH(1, 1, 1, 1, 1); break;
-	}
-#undef PL_LAUNCH
+		pl = std::max(pl, gg_join_keeps_unmatched(p.pl.jkind[j]) ? 2
+			      : gg_join_builds_map(p.pl.jkind[j]) ? 1 : 0);
+	PL_TABLE[pl_encode(nt && nt[0] == '1', mm, pl,
+			   /* a packed pair of group columns */
+			   p.ngroup == 2 && p.gp.packed,
+			   /* some aggregate carries a filter */
+			   p.fl.used != 0)](s, p);
 	return hipGetLastError();
 }
 

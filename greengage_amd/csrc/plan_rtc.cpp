@@ -466,6 +466,90 @@ static void emit_prelude(std::string &s, const Gen &G)
 	s += DEVICE_FNS;
 }
 
+/* ---- one join of the row filter ----
+ * The open-addressing probe of P.joins[<j>] (J) for key k<j> (k): keys are
+ * stored as key ^ msb, 0 = empty.  `hit` and `miss` are the statements on a
+ * matching and on an empty slot, `after` the text behind the loop.  With
+ * empty_first a probe key of INT64_MIN (encoded 0 = the empty sentinel)
+ * finds nothing and never reads an unwritten index */
+static void emit_hash_probe(std::string &s, const std::string &k,
+			    const std::string &J, bool empty_first,
+			    const std::string &hit, const std::string &miss,
+			    const std::string &after = "")
+{
+	const std::string e = "\t\t\t\tif (cur == 0) " + miss + "\n";
+	const std::string m = "\t\t\t\tif (cur == t) " + hit + "\n";
+
+	s += "\t\t{\n\t\t\tunsigned long long t = (unsigned long long) " + k +
+		" ^ 0x8000000000000000ull;\n\t\t\tuint64_t pos = (uint64_t) "
+		"gg_hashint8(" + k + ") & (" + J + ".hslots - 1);\n"
+		"\t\t\tfor (;;) {\n\t\t\t\tunsigned long long cur = " + J +
+		".hkeys[pos];\n" + (empty_first ? e + m : m + e) +
+		"\t\t\t\tpos = (pos + 1) & (" + J + ".hslots - 1);\n\t\t\t}\n" +
+		after + "\t\t}\n";
+}
+
+static void emit_join(std::string &s, const PlanDev &D, int j)
+{
+	const int kind = D.pl.jkind[j], ps = D.pl.jpsrc[j];
+	const bool map = gg_join_builds_map(kind);
+	const bool keep = gg_join_keeps_unmatched(kind);
+	const std::string pi = ix_of(ps), k = fmt("k%d", j), r = fmt("r%d", j),
+		J = fmt("P.joins[%d]", j), take = r + fmt(" = P.pl.jidx[%d]", j),
+		in = k + " >= 0 && " + k + " < " + J + ".dlen",
+		out = k + " < 0 || " + k + " >= " + J + ".dlen", no = "return false;";
+	/* The probe key is NULL where its source, an earlier LEFT join,
+	 * NULL-extended the row (hs clear), or by its own flag nf; the source
+	 * is tested first, which keeps the flag load behind it.  SEMI and INNER
+	 * drop such a row (NULL never matches); LEFT and ANTI skip the probe:
+	 * LEFT NULL-extends and ANTI keeps the row */
+	const std::string hs = left_src(D, ps) ? fmt("h%d", ps - 1) : "",
+		nf = D.joins[j].pnulls ? J + ".pnulls[" + pi + "]" : "";
+
+	if (kind == GG_JOIN_LEFT)
+		s += "\t\t" + r + " = 0xFFFFFFFFu;\n";
+	if (!keep)
+		s += (hs.empty() ? "" : "\t\tif (!" + hs + ") " + no + "\n") +
+			(nf.empty() ? "" : "\t\tif (" + nf + ") " + no + "\n");
+	else if (hs.empty() && nf.empty())
+		s += "\t\t{\n";
+	else
+		s += "\t\tif (" + hs + (hs.empty() || nf.empty() ? "" : " && ") +
+			(nf.empty() ? "" : "!" + nf) + ")\n\t\t{\n";
+	/* a gathered probe key (chained join) is never streamed */
+	emit_ld(s, k.c_str(), (J + ".pkey").c_str(), D.joins[j].width,
+		pi.c_str());
+	if (map && D.joins[j].dlen)
+		/* dense index map: the range check comes before the map is
+		 * touched; 0xFFFFFFFF = no build row, LEFT's "no partner" */
+		s += keep ? "\t\tif (" + in + ")\n\t\t\t" + take + "[" + k + "];\n"
+			: "\t\tif (" + out + ")\n\t\t\t" + no + "\n\t\t" + take + "[" +
+			  k + "];\n\t\tif (" + r + " == 0xFFFFFFFFu) " + no + "\n";
+	else if (!map && D.joins[j].bits)
+		/* SEMI drops a non-member; ANTI is the same test, inverted */
+		s += "\t\tif (" + (keep ? in + " &&" : out + " ||") + "\n\t\t    " +
+			(keep ? "" : "!") + "((" + J + ".bits[" + k + " >> 6] >> (" +
+			k + " & 63)) & 1))\n\t\t\t" + no + "\n";
+	else if (kind == GG_JOIN_SEMI)
+		/* match before empty, as ever: an INT64_MIN probe key "matches"
+		 * the first empty slot (LEFT OUTER and ANTI joins) */
+		emit_hash_probe(s, k, J, false, "break;", no);
+	else if (kind == GG_JOIN_INNER)
+		emit_hash_probe(s, k, J, true, "break;", no,
+				"\t\t\t" + take + "[pos];\n");
+	else if (kind == GG_JOIN_LEFT)
+		emit_hash_probe(s, k, J, true, "{ " + take + "[pos]; break; }",
+				"break;");
+	else
+		emit_hash_probe(s, k, J, true, no, "break;");
+	if (kind == GG_JOIN_LEFT)
+		/* close the probe, then the row's one "has a partner" flag */
+		s += "\t\t}\n\t\th" + std::to_string(j) + " = " + r +
+			" != 0xFFFFFFFFu;\n";
+	else if (keep)
+		s += "\t\t}\n";
+}
+
 /* ---- per-row evaluation as a macro-free inline sequence ---- */
 static void emit_row_pass(std::string &s, const Gen &G)
 {
@@ -487,122 +571,7 @@ static void emit_row_pass(std::string &s, const Gen &G)
 			 p, p, p, p);
 	}
 	for (int j = 0; j < D.njoins; j++)
-	{
-		std::string pi = ix_of(D.pl.jpsrc[j]);
-		const int kind = D.pl.jkind[j];
-		const bool psl = left_src(D, D.pl.jpsrc[j]);
-
-		if (kind == GG_JOIN_LEFT || kind == GG_JOIN_ANTI)
-		{
-			/* Neither kind drops a row for a NULL probe key: the
-			 * probe is skipped, LEFT NULL-extends and ANTI keeps
-			 * the row.  The key is NULL by its own flag or because
-			 * its source, an earlier LEFT join, NULL-extended the
-			 * row; `&&` keeps the flag load behind that test */
-			std::string c = psl ? fmt("h%d", D.pl.jpsrc[j] - 1) : "";
-
-			if (D.joins[j].pnulls)
-				c += fmt("%s!P.joins[%d].pnulls[%s]",
-					 psl ? " && " : "", j, pi.c_str());
-			if (kind == GG_JOIN_LEFT)
-				s += fmt("\t\tr%d = 0xFFFFFFFFu;\n", j);
-			s += c.empty() ? "\t\t{\n"
-				: fmt("\t\tif (%s)\n\t\t{\n", c.c_str());
-			emit_ld(s, fmt("k%d", j).c_str(),
-				fmt("P.joins[%d].pkey", j).c_str(), D.joins[j].width,
-				pi.c_str());
-			if (kind == GG_JOIN_LEFT && D.joins[j].dlen)
-				/* dense index map: a key outside [0, dlen) has
-				 * no partner; the range check comes before the
-				 * map is touched */
-				s += fmt("\t\tif (k%d >= 0 && k%d < P.joins[%d].dlen)\n"
-					 "\t\t\tr%d = P.pl.jidx[%d][k%d];\n",
-					 j, j, j, j, j, j);
-			else if (kind == GG_JOIN_LEFT)
-				/* hash map, EMPTY before match: a probe key of
-				 * INT64_MIN finds nothing */
-				s += fmt("\t\t{\n"
-					 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
-					 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
-					 "\t\t\tfor (;;) {\n"
-					 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
-					 "\t\t\t\tif (cur == 0) break;\n"
-					 "\t\t\t\tif (cur == t) { r%d = P.pl.jidx[%d][pos]; break; }\n"
-					 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
-					 "\t\t\t}\n\t\t}\n",
-					 j, j, j, j, j, j, j);
-			else if (D.joins[j].bits)
-				/* ANTI: the SEMI membership test, inverted */
-				s += fmt("\t\tif (k%d >= 0 && k%d < P.joins[%d].dlen &&\n"
-					 "\t\t    ((P.joins[%d].bits[k%d >> 6] >> (k%d & 63)) & 1))\n"
-					 "\t\t\treturn false;\n", j, j, j, j, j, j);
-			else
-				s += fmt("\t\t{\n"
-					 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
-					 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
-					 "\t\t\tfor (;;) {\n"
-					 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
-					 "\t\t\t\tif (cur == 0) break;\n"
-					 "\t\t\t\tif (cur == t) return false;\n"
-					 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
-					 "\t\t\t}\n\t\t}\n", j, j, j, j, j);
-			s += "\t\t}\n";
-			if (kind == GG_JOIN_LEFT)
-				/* the row's one "has a partner" flag */
-				s += fmt("\t\th%d = r%d != 0xFFFFFFFFu;\n", j, j);
-			continue;
-		}
-		if (psl)
-			/* SEMI / INNER through a NULL-extended row: the probe
-			 * key is NULL and never matches */
-			s += fmt("\t\tif (!h%d) return false;\n",
-				 D.pl.jpsrc[j] - 1);
-		if (D.joins[j].pnulls)
-			s += fmt("\t\tif (P.joins[%d].pnulls[%s]) return false;\n",
-				 j, pi.c_str());
-		/* a gathered probe key (chained join) is never streamed */
-		emit_ld(s, fmt("k%d", j).c_str(),
-			fmt("P.joins[%d].pkey", j).c_str(), D.joins[j].width,
-			pi.c_str());
-		if (D.pl.jkind[j] == GG_JOIN_INNER && D.joins[j].dlen)
-			/* dense index map: range check before the map is
-			 * touched, 0xFFFFFFFF = no build row */
-			s += fmt("\t\tif (k%d < 0 || k%d >= P.joins[%d].dlen)\n"
-				 "\t\t\treturn false;\n"
-				 "\t\tr%d = P.pl.jidx[%d][k%d];\n"
-				 "\t\tif (r%d == 0xFFFFFFFFu) return false;\n",
-				 j, j, j, j, j, j, j);
-		else if (D.pl.jkind[j] == GG_JOIN_INNER)
-			/* key -> index hash map; EMPTY is tested BEFORE the
-			 * match so a probe key of INT64_MIN (encoded 0 = the
-			 * empty sentinel) finds nothing and never reads an
-			 * unwritten index */
-			s += fmt("\t\t{\n"
-				 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
-				 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
-				 "\t\t\tfor (;;) {\n"
-				 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
-				 "\t\t\t\tif (cur == 0) return false;\n"
-				 "\t\t\t\tif (cur == t) break;\n"
-				 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
-				 "\t\t\t}\n"
-				 "\t\t\tr%d = P.pl.jidx[%d][pos];\n\t\t}\n",
-				 j, j, j, j, j, j, j);
-		else if (D.joins[j].bits)
-			s += fmt("\t\tif (k%d < 0 || k%d >= P.joins[%d].dlen ||\n"
-				 "\t\t    !((P.joins[%d].bits[k%d >> 6] >> (k%d & 63)) & 1))\n"
-				 "\t\t\treturn false;\n", j, j, j, j, j, j);
-		else
-			s += fmt("\t\t{\n"
-				 "\t\t\tunsigned long long t = (unsigned long long) k%d ^ 0x8000000000000000ull;\n"
-				 "\t\t\tuint64_t pos = (uint64_t) gg_hashint8(k%d) & (P.joins[%d].hslots - 1);\n"
-				 "\t\t\tfor (;;) {\n"
-				 "\t\t\t\tunsigned long long cur = P.joins[%d].hkeys[pos];\n"
-				 "\t\t\t\tif (cur == t) break;\n"
-				 "\t\t\t\tif (cur == 0) return false;\n"
-				 "\t\t\t\tpos = (pos + 1) & (P.joins[%d].hslots - 1);\n"
-				 "\t\t\t}\n\t\t}\n", j, j, j, j, j);
-	}
+		emit_join(s, D, j);
 	s += "\t\treturn true;\n\t};\n";
 }
 
@@ -1188,8 +1157,7 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	bool payload = false;
 
 	for (int j = 0; j < D.njoins; j++)
-		if (D.pl.jkind[j] == GG_JOIN_INNER ||
-		    D.pl.jkind[j] == GG_JOIN_LEFT)
+		if (gg_join_builds_map(D.pl.jkind[j]))
 			payload = true;
 	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt, payload};
 	std::string s;

@@ -39,6 +39,13 @@
  *   year   plan_outer_bench.py's `year`: dense INNER join, grouped by an
  *          int32 payload column; generic + baked fast tier
  *   yearl  the same with the join made LEFT (`year_left`)
+ *   innh   global-group plan: hashed INNER join with a nullable probe key,
+ *          and a bitmap ANTI join chained through it whose only condition
+ *          is its own nullable probe key
+ *   lsemi  dense LEFT join, and a hashed SEMI join chained through it
+ *   linner hashed LEFT join, and a dense INNER join chained through it
+ *   ll     dense LEFT join, and a dense LEFT join chained through it
+ *   lln    the same with the second join hashed on a nullable probe key
  *   all    every shape above, DUMPFILE used as a prefix: <prefix><shape>.cu
  * Exit status is non-zero when a variant fails to COMPILE (a module
  * load / function lookup failure without a GPU is not a failure). */
@@ -193,6 +200,41 @@ set_afilt(PlanDev &D, int a, int k)
 	D.fl.used |= 1 << k;
 }
 
+/* join j of the given kind probes the `width`-byte column at dummy + 144
+ * (join 0) or dummy + 160 (join 1) of source `psrc`; pnulls != 0 makes that
+ * key nullable, its flags at dummy + pnulls */
+static PlanJoinDev &
+set_join(PlanDev &D, int j, int kind, int width, int pnulls = 0, int psrc = 0)
+{
+	D.njoins = j + 1;
+	D.joins[j].pkey = dummy + 144 + 16 * j;
+	D.joins[j].width = width;
+	if (pnulls)
+		D.joins[j].pnulls = (const uint8_t *) dummy + pnulls;
+	D.pl.jkind[j] = (int8_t) kind;
+	D.pl.jpsrc[j] = (int8_t) psrc;
+	if (gg_join_builds_map(kind))
+		D.pl.jidx[j] = (const uint32_t *) (dummy + 152);
+	return D.joins[j];
+}
+
+/* the three build-side structures: a dense key range (INNER / LEFT: index
+ * map, SEMI / ANTI: bitmap at dummy + bits) or an open-addressing table */
+static void
+join_dense(PlanJoinDev &J, int bits = 0)
+{
+	J.dlen = 1000;
+	if (bits)
+		J.bits = (const unsigned long long *) (dummy + bits);
+}
+
+static void
+join_hash(PlanJoinDev &J)
+{
+	J.hkeys = (const unsigned long long *) (dummy + 176);
+	J.hslots = 1024;
+}
+
 /* compile errors come back as GG_ENOTSUP with this message prefix */
 static bool
 compiled(gg_status s)
@@ -238,12 +280,7 @@ dump_shape(const char *shape, const char *file)
 
 		shape_q6(D, false);
 		D.npreds = 1;
-		D.njoins = 1;
-		D.joins[0].pkey = dummy + 144;
-		D.joins[0].width = 8;
-		D.joins[0].dlen = 1000;
-		D.pl.jkind[0] = GG_JOIN_INNER;
-		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
+		join_dense(set_join(D, 0, GG_JOIN_INNER, 8));
 		D.naggs = 3;
 		set_agg(D, 0, 2, 2, c_pd, m_pd);
 		set_agg(D, 1, 2, 2, c_pd, m_pd);
@@ -272,16 +309,8 @@ dump_shape(const char *shape, const char *file)
 	else if (!std::strcmp(shape, "join"))
 	{
 		shape_q6(D, false);
-		D.njoins = 2;
-		D.joins[0].pkey = dummy + 144;
-		D.joins[0].width = 8;
-		D.joins[0].bits = (const unsigned long long *) (dummy + 152);
-		D.joins[0].dlen = 1000;
-		D.joins[1].pkey = dummy + 160;
-		D.joins[1].pnulls = (const uint8_t *) dummy + 168;
-		D.joins[1].width = 4;
-		D.joins[1].hkeys = (const unsigned long long *) (dummy + 176);
-		D.joins[1].hslots = 1024;
+		join_dense(set_join(D, 0, GG_JOIN_SEMI, 8), 152);
+		join_hash(set_join(D, 1, GG_JOIN_SEMI, 4, 168));
 	}
 	else if (!std::strcmp(shape, "left"))
 	{
@@ -289,19 +318,8 @@ dump_shape(const char *shape, const char *file)
 		 * the build table of a dense LEFT join; a hashed ANTI join
 		 * chained through a nullable payload column of it */
 		shape_g1(D, 4, false);
-		D.njoins = 2;
-		D.joins[0].pkey = dummy + 144;
-		D.joins[0].width = 8;
-		D.joins[0].dlen = 1000;
-		D.pl.jkind[0] = GG_JOIN_LEFT;
-		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
-		D.joins[1].pkey = dummy + 160;
-		D.joins[1].pnulls = (const uint8_t *) dummy + 168;
-		D.joins[1].width = 4;
-		D.joins[1].hkeys = (const unsigned long long *) (dummy + 176);
-		D.joins[1].hslots = 1024;
-		D.pl.jkind[1] = GG_JOIN_ANTI;
-		D.pl.jpsrc[1] = 1;
+		join_dense(set_join(D, 0, GG_JOIN_LEFT, 8));
+		join_hash(set_join(D, 1, GG_JOIN_ANTI, 4, 168, 1));
 		D.pl.gsrc[0] = 1;
 		D.pl.asrc[1][0] = 1;
 		D.aggs[1].nulls[0] = (const uint8_t *) dummy + 128;
@@ -325,12 +343,8 @@ dump_shape(const char *shape, const char *file)
 			1996, 1997, 1998};
 
 		D.n = 600000000;
-		D.njoins = 1;
-		D.joins[0].pkey = dummy + 144;
-		D.joins[0].width = 8;
-		D.joins[0].dlen = 1000;
-		D.pl.jkind[0] = shape[4] ? GG_JOIN_LEFT : GG_JOIN_INNER;
-		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
+		join_dense(set_join(D, 0, shape[4] ? GG_JOIN_LEFT : GG_JOIN_INNER,
+				    8));
 		D.ngroup = 1;
 		D.gcol[0] = dummy + 8;
 		D.gwidth[0] = 4;
@@ -350,25 +364,59 @@ dump_shape(const char *shape, const char *file)
 		static const int m_id[] = {0, 0};
 
 		shape_q6(D, false);
-		D.njoins = 2;
-		D.joins[0].pkey = dummy + 144;
-		D.joins[0].pnulls = (const uint8_t *) dummy + 168;
-		D.joins[0].width = 8;
-		D.joins[0].hkeys = (const unsigned long long *) (dummy + 176);
-		D.joins[0].hslots = 1024;
-		D.pl.jkind[0] = GG_JOIN_LEFT;
-		D.pl.jidx[0] = (const uint32_t *) (dummy + 152);
-		D.joins[1].pkey = dummy + 160;
-		D.joins[1].width = 4;
-		D.joins[1].bits = (const unsigned long long *) (dummy + 216);
-		D.joins[1].dlen = 1000;
-		D.pl.jkind[1] = GG_JOIN_ANTI;
+		join_hash(set_join(D, 0, GG_JOIN_LEFT, 8, 168));
+		join_dense(set_join(D, 1, GG_JOIN_ANTI, 4), 216);
 		D.naggs = 3;
 		set_agg(D, 0, 2, 2, c_pd, m_id);
 		D.pl.asrc[0][1] = 1;
 		set_agg(D, 1, 0, 0, nullptr, nullptr);
 		set_agg(D, 2, 1, 1, c_q, m_id);
 		D.pl.asrc[2][0] = 1;
+	}
+	else if (!std::strcmp(shape, "innh") || !std::strcmp(shape, "lsemi") ||
+		 !std::strcmp(shape, "linner") || !std::strcmp(shape, "ll") ||
+		 !std::strcmp(shape, "lln"))
+	{
+		/* global-group plans whose second join is chained through the
+		 * first: SUM(driving x payload of join 0), COUNT(*), and where
+		 * join 1 has a payload too, COUNT(payload of join 1) */
+		static const int c_pd[] = {PRICE, DISC}, c_q[] = {QTY};
+		static const int m_id[] = {0, 0};
+
+		shape_q6(D, false);
+		if (!std::strcmp(shape, "innh"))
+		{
+			join_hash(set_join(D, 0, GG_JOIN_INNER, 8, 168));
+			join_dense(set_join(D, 1, GG_JOIN_ANTI, 4, 224, 1), 216);
+		}
+		else if (!std::strcmp(shape, "lsemi"))
+		{
+			join_dense(set_join(D, 0, GG_JOIN_LEFT, 8));
+			join_hash(set_join(D, 1, GG_JOIN_SEMI, 4, 0, 1));
+		}
+		else if (!std::strcmp(shape, "linner"))
+		{
+			join_hash(set_join(D, 0, GG_JOIN_LEFT, 8));
+			join_dense(set_join(D, 1, GG_JOIN_INNER, 4, 0, 1));
+		}
+		else
+		{
+			join_dense(set_join(D, 0, GG_JOIN_LEFT, 8));
+			if (shape[2])
+				join_hash(set_join(D, 1, GG_JOIN_LEFT, 4, 224, 1));
+			else
+				join_dense(set_join(D, 1, GG_JOIN_LEFT, 4, 0, 1));
+		}
+		D.naggs = 2;
+		set_agg(D, 0, 2, 2, c_pd, m_id);
+		D.pl.asrc[0][1] = 1;
+		set_agg(D, 1, 0, 0, nullptr, nullptr);
+		if (D.pl.jidx[1])
+		{
+			D.naggs = 3;
+			set_agg(D, 2, 1, 1, c_q, m_id);
+			D.pl.asrc[2][0] = 2;
+		}
 	}
 	else if (!std::strcmp(shape, "pnull"))
 	{
@@ -436,7 +484,8 @@ main(int argc, char **argv)
 {
 	static const char *const all[] = {"q1", "q1w", "q6", "q1mm", "q1mmw",
 		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl", "q1f", "pvf",
-		"left", "lefth", "year", "yearl"};
+		"left", "lefth", "year", "yearl", "innh", "lsemi", "linner", "ll",
+		"lln"};
 	const char *file = argc > 1 ? argv[1] : "/tmp/rtc_dump.cu";
 	const char *shape = argc > 2 ? argv[2] : "q1";
 	bool ok = true;
