@@ -16,9 +16,12 @@ from .engine import (  # noqa: F401
     PGDate,
     PLAN_MAX_FILTERS,
     PLAN_MAX_FILTER_PREDS,
+    PLAN_MAX_LIMIT,
+    PLAN_MAX_ORDER,
     build_plan_desc,
     pgdate,
     plan_group_bits,
+    plan_topk_tile,
 )
 
 __version__ = "0.1.0"

@@ -174,6 +174,15 @@ struct Pipeline
 		return p;
 	}
 
+	/* bytes a named scratch buffer holds now (0 = none yet) */
+	size_t ssize(const char *name) const
+	{
+		for (auto &kv : scratch)
+			if (kv.first == name && kv.second.first)
+				return kv.second.second;
+		return 0;
+	}
+
 	~Pipeline()
 	{
 		for (auto &kv : scratch)
@@ -739,6 +748,96 @@ hipError_t launch_plan_compact(hipStream_t s,
 			       uint64_t nslots, int naggs,
 			       unsigned long long *out,
 			       unsigned long long *out_n, uint64_t cap);
+
+/* The group keys a code stands for (a NULL key is GG_PLAN_NULL_KEY).  ONE
+ * definition for both sides: plan.cpp decodes every arena row with it, and
+ * the device top-k (plan_topk.hip) decodes the order's key entries with it,
+ * so the host comparator and the device sort keys cannot drift apart. */
+__host__ __device__ static inline void
+plan_keys_of(const PlanGroupPackDev &G, int ngroup, long long code,
+	     int64_t *k0, int64_t *k1)
+{
+	if (G.packed)
+	{
+		/* (e0 << shift) | e1; e = 0 is NULL, else the
+		 * value's offset from the column minimum, plus 1 */
+		uint64_t e0 = (uint64_t) code >> G.shift;
+		uint64_t e1 = (uint64_t) code & ((1ull << G.shift) - 1);
+
+		*k0 = e0 ? (int64_t) ((uint64_t) G.gmin[0] + e0 - 1)
+			: GG_PLAN_NULL_KEY;
+		*k1 = e1 ? (int64_t) ((uint64_t) G.gmin[1] + e1 - 1)
+			: GG_PLAN_NULL_KEY;
+	}
+	else if (ngroup == 2)
+	{
+		long long e0 = code / 512, e1 = code % 512;
+
+		*k0 = e0 == 256 ? GG_PLAN_NULL_KEY : e0;
+		*k1 = e1 == 256 ? GG_PLAN_NULL_KEY : e1;
+	}
+	else
+	{
+		*k0 = code;
+		*k1 = 0;
+	}
+}
+
+/* ---- device top-k over the compacted group rows (plan_topk.hip) ----
+ * One resolved entry of gg_plan_desc.order[]: which words of a compacted
+ * row (code, naggs x (lo, hi)) it reads and how they compare. */
+enum PlanOrderKind
+{
+	PL_ORD_KEY = 0,		/* decoded group key `slot` (0 or 1) */
+	PL_ORD_I128 = 1,	/* COUNT / SUM: accumulator `slot`, signed
+				 * 128-bit, never NULL */
+	PL_ORD_MIN = 2,		/* MIN / MAX: order-encoded word in `slot`, */
+	PL_ORD_MAX = 3		/* non-NULL count in `cnt` (0 = NULL) */
+};
+
+struct PlanOrderEnt
+{
+	int8_t kind;		/* PlanOrderKind */
+	int8_t desc;
+	int8_t nulls_first;
+	int8_t slot;
+	int8_t cnt;
+};
+
+struct PlanTopkDev
+{
+	const unsigned long long *rows;	/* ng compacted rows */
+	uint64_t ng;
+	int rowsz;		/* u64 words per row */
+	int norder;
+	int limit;		/* 1 .. GG_PLAN_MAX_LIMIT */
+	int ngroup;
+	PlanGroupPackDev gp;
+	PlanOrderEnt ord[GG_PLAN_MAX_ORDER];
+};
+
+/* rows per tournament tile, threads per tile, "no row" */
+#define PL_TOPK_TILE 2048
+#define PL_TOPK_THREADS 1024
+#define PL_TOPK_PAD 0xFFFFFFFFu
+static_assert(PL_TOPK_TILE >= 2 * GG_PLAN_MAX_LIMIT &&
+	      (PL_TOPK_TILE & (PL_TOPK_TILE - 1)) == 0,
+	      "a tile holds two tiles' survivors and is a power of two");
+
+/* LDS bytes of one tile for an order of `norder` entries */
+size_t plan_topk_lds_bytes(int norder);
+/* One tournament round over n candidates: src[0..n) are row indices
+ * (nullptr = the rows 0..n-1 themselves; PL_TOPK_PAD entries are skipped),
+ * every tile of PL_TOPK_TILE candidates writes the indices of its first
+ * K.limit rows, in order and padded with PL_TOPK_PAD, to dst[tile * K.limit
+ * ...]; dst holds ceil(n / PL_TOPK_TILE) * K.limit entries. */
+hipError_t launch_plan_topk_round(hipStream_t s, const PlanTopkDev &K,
+				  const uint32_t *src, uint64_t n,
+				  uint32_t *dst);
+/* out[j] = row idx[j] for j < K.limit (zeros for a PL_TOPK_PAD entry) */
+hipError_t launch_plan_topk_gather(hipStream_t s, const PlanTopkDev &K,
+				   const uint32_t *idx,
+				   unsigned long long *out);
 
 /* plan.cpp */
 gg_status exec_plan(Pipeline *p, void *arena, size_t bytes,

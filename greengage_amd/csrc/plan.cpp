@@ -76,6 +76,16 @@ struct PlanResolved
 	 * widths are kept for the refusal's message */
 	int gp_state = 0;
 	int gp_bits[2] = {0, 0};
+	/* ORDER BY / LIMIT (gg_plan_desc.order / limit), the order's entries
+	 * resolved onto compacted-row words; the device top-k reads the same
+	 * entries (engine_internal.h PlanOrderEnt) */
+	PlanOrderEnt ord[GG_PLAN_MAX_ORDER] = {};
+	int norder = 0;
+	int64_t limit = 0;
+	/* gg_plan_desc.est_groups, and the group table's slot count once an
+	 * execute has settled it (0 = not yet) */
+	int64_t est_groups = 0;
+	uint64_t nslots = 0;
 };
 
 static int coltype_width(gg_coltype t)
@@ -187,6 +197,13 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 	    d->nfilters < 0 || d->nfilters > GG_PLAN_MAX_FILTERS)
 		return fail(GG_ENOTSUP, "plan: shape out of v1 bounds "
 			    "(fall back to standard_ExecutorRun)");
+
+	if (d->limit < 0 || d->norder < 0 || d->norder > GG_PLAN_MAX_ORDER ||
+	    d->est_groups < 0)
+		return fail(GG_ENOTSUP, "plan: limit %lld, %d order entries or "
+			    "est_groups %lld out of bounds (fall back to "
+			    "standard_ExecutorRun)", (long long) d->limit,
+			    d->norder, (long long) d->est_groups);
 
 	auto pr = std::make_shared<PlanResolved>();
 	PlanResolved *R = pr.get();
@@ -444,6 +461,47 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 					col_bytes(R->dev.fl.preds[k][i].col,
 						  R->dev.fl.psrc[k][i],
 						  R->dev.fl.preds[k][i].width);
+
+	/* the order's entries, onto the words of a compacted row */
+	for (int o = 0; o < d->norder; o++)
+	{
+		const gg_plan_order *O = &d->order[o];
+		PlanOrderEnt &E = R->ord[o];
+
+		E.desc = O->desc != 0;
+		E.nulls_first = O->nulls_first != 0;
+		if (O->what == 0)
+		{
+			if (O->index < 0 || O->index >= d->ngroup)
+				return fail(GG_EINVAL, "plan: order entry %d names "
+					    "group key %d, the plan has %d", o,
+					    O->index, d->ngroup);
+			E.kind = PL_ORD_KEY;
+			E.slot = O->index;
+		}
+		else if (O->what == 1)
+		{
+			if (O->index < 0 || O->index >= d->naggs)
+				return fail(GG_EINVAL, "plan: order entry %d names "
+					    "aggregate %d, the plan has %d", o,
+					    O->index, d->naggs);
+			const PlanResolved::OutAgg &A = R->outs[O->index];
+
+			if (A.kind == GG_AGG_AVG)
+				return fail(GG_ENOTSUP, "plan: order entry %d: an "
+					    "AVG cannot be an order key", o);
+			E.kind = A.kind == GG_AGG_MIN ? PL_ORD_MIN
+				: A.kind == GG_AGG_MAX ? PL_ORD_MAX : PL_ORD_I128;
+			E.slot = (int8_t) A.slot;
+			E.cnt = (int8_t) (A.cnt < 0 ? 0 : A.cnt);
+		}
+		else
+			return fail(GG_EINVAL, "plan: order entry %d: what = %d",
+				    o, O->what);
+	}
+	R->norder = d->norder;
+	R->limit = d->limit;
+	R->est_groups = d->est_groups;
 
 	Pipeline *p = new Pipeline();
 
@@ -800,35 +858,84 @@ plan_build_joins(Engine &e, Pipeline *p, PlanResolved *R,
 	return GG_OK;
 }
 
-/* 2. group table + fused scan, 3. compact: leaves the segment's groups in
- * *dout_p and, copied to the host, in `rows`.  The first execute compiles the
- * plan's generated kernel; a baked kernel that misses is dropped and the
- * execute redone on the generic one */
+/* 2. group table + fused scan, 3. compact: leaves the segment's *ng_p groups
+ * in *dout_p, on the device.  The first execute compiles the plan's generated
+ * kernel; a baked kernel that misses is dropped and the execute redone on the
+ * generic one; a table sized from an estimate that fills is regrown */
 static gg_status
 plan_scan_groups(Engine &e, Pipeline *p, PlanResolved *R,
 		 unsigned long long *ctr, unsigned long long **dout_p,
-		 std::vector<unsigned long long> &rows)
+		 unsigned long long *ng_p)
 {
-	uint64_t nslots = R->dev.ngroup == 0 ? 1
+	/* the fixed table: what every plan without an estimate gets */
+	const uint64_t fixed = R->dev.ngroup == 0 ? 1
 		: (R->dev.ngroup == 2 ? 1 << 19 : PL_NSLOTS);
+	/* with an estimate (gg_plan_desc.est_groups) the table starts at the
+	 * estimate and may grow up to `ceiling` slots; there are never more
+	 * groups than driving rows, so a table of 2 * rows slots cannot fill */
+	const bool growable = R->est_groups > 0 && R->dev.ngroup > 0;
+	const uint64_t rows2 = 2 * (uint64_t) std::max<int64_t>(R->scan_rows, 0);
+	const uint64_t ceiling = std::max(fixed, next_pow2_pl(rows2));
+	uint64_t nslots = R->nslots;
 	int naggs = R->dev.naggs;
-	uint64_t cap = nslots;
 	int rowsz = plan_rowsz(R);
-	unsigned long long *tkeys = (unsigned long long *)
-		p->sget("plan.tkeys", nslots * 8);
-	unsigned long long *tvals = (unsigned long long *)
-		p->sget("plan.tvals", nslots * (size_t) naggs * 16);
-	unsigned long long *dout = (unsigned long long *)
-		p->sget("plan.out", cap * (size_t) rowsz * 8);
+	unsigned long long *dout = nullptr;
 	unsigned long long ng = 0, herr = 0;
 
-	if (!tkeys || !tvals)
-		return fail(GG_ENOMEM, "plan group table");
-	if (!dout)
-		return fail(GG_ENOMEM, "plan out");
-	R->dev.tkeys = tkeys;
-	R->dev.tvals = tvals;
-	R->dev.nslots = nslots;
+	if (!nslots)
+		nslots = !growable ? fixed
+			: std::max(fixed, next_pow2_pl(std::min(
+				2 * (uint64_t) R->est_groups, rows2)));
+
+	/* the table and the compacted output (cap = nslots rows) for the
+	 * current nslots.  A growable table is checked against the free
+	 * device memory first, counting what the buffers it replaces give
+	 * back, and refused rather than left to a failing allocation */
+	auto table_alloc = [&]() -> gg_status
+	{
+		const size_t kb = nslots * 8, vb = nslots * (size_t) naggs * 16,
+			ob = nslots * (size_t) rowsz * 8;
+
+		if (growable && nslots > fixed)
+		{
+			size_t fr = 0, tot = 0, held = 0, need = 0;
+			const char *nm[3] = {"plan.tkeys", "plan.tvals",
+					     "plan.out"};
+			const size_t want[3] = {kb, vb, ob};
+
+			for (int i = 0; i < 3; i++)
+				if (p->ssize(nm[i]) < want[i])
+				{
+					held += p->ssize(nm[i]);
+					need += want[i];
+				}
+			GG_HIP(hipMemGetInfo(&fr, &tot));
+			if (need > fr + held)
+				return fail(GG_ENOTSUP,
+					    "plan: a group table of %llu slots "
+					    "needs %zu bytes with its output, %zu "
+					    "are free (fall back to "
+					    "standard_ExecutorRun)",
+					    (unsigned long long) nslots, need,
+					    fr + held);
+		}
+		unsigned long long *tkeys = (unsigned long long *)
+			p->sget("plan.tkeys", kb);
+		unsigned long long *tvals = (unsigned long long *)
+			p->sget("plan.tvals", vb);
+
+		dout = (unsigned long long *) p->sget("plan.out", ob);
+		if (!tkeys || !tvals)
+			return fail(GG_ENOMEM, "plan group table");
+		if (!dout)
+			return fail(GG_ENOMEM, "plan out");
+		R->dev.tkeys = tkeys;
+		R->dev.tvals = tvals;
+		R->dev.nslots = nslots;
+		return GG_OK;
+	};
+
+	GG_TRY(table_alloc());
 	{
 		Timed tm(e.stream);
 
@@ -868,20 +975,48 @@ plan_scan_groups(Engine &e, Pipeline *p, PlanResolved *R,
 		GG_TRY(plan_scan_compact(e, p, R, R->rtc, nullptr, dout, ctr,
 					 &herr));
 	}
+	/* the estimate was too low and the table filled: redo the scan on a
+	 * table four times the size, until it fits.  The duplicate-key bit
+	 * was dealt with above, so the error word can be cleared whole.  The
+	 * attempt that filled the table was slow by construction (every late
+	 * row probed all of it, pl_slot): the price of an underestimate */
+	while (growable && (herr & PL_ERR_FULL) && nslots < ceiling)
+	{
+		nslots = std::min(nslots * 4, ceiling);
+		p->stat("path_plan_group_grow").launches++;
+		GG_TRY(table_alloc());
+		GG_HIP(hipMemsetAsync(R->dev.err, 0, 8, e.stream));
+		Timed tm(e.stream);
+
+		GG_TRY(plan_reset_table(e.stream, R->dev));
+		GG_TRY(plan_scan_compact(e, p, R,
+					 R->rtc_baked ? R->rtc_baked : R->rtc,
+					 &tm, dout, ctr, &herr));
+	}
 	if (herr)
 		return fail(GG_EINVAL,
 			    "plan: group cardinality exceeds %llu "
 			    "(generic-path v1 cap)",
 			    (unsigned long long) nslots / 2);
+	/* tables are immutable: later executes start where this one ended */
+	R->nslots = nslots;
 	GG_HIP(hipMemcpy(&ng, ctr, 8, hipMemcpyDeviceToHost));
-	if (ng > cap)
+	if (ng > nslots)
 		return fail(GG_ESTATE, "plan compact overflow");
+	*dout_p = dout;
+	*ng_p = ng;
+	return GG_OK;
+}
 
-	rows.resize((size_t) ng * rowsz);
+/* the whole compacted result, copied to the host */
+static gg_status
+plan_fetch_rows(const PlanResolved *R, const unsigned long long *dout,
+		unsigned long long ng, std::vector<unsigned long long> &rows)
+{
+	rows.resize((size_t) ng * plan_rowsz(R));
 	if (ng)
 		GG_HIP(hipMemcpy(rows.data(), dout, rows.size() * 8,
 				 hipMemcpyDeviceToHost));
-	*dout_p = dout;
 	return GG_OK;
 }
 
@@ -991,54 +1126,116 @@ plan_combine_segments(Engine &e, Pipeline *p, const PlanResolved *R,
 static void
 plan_keys_of(const PlanDev &D, long long code, int64_t *k0, int64_t *k1)
 {
-	if (D.gp.packed)
-	{
-		/* (e0 << shift) | e1; e = 0 is NULL, else the
-		 * value's offset from the column minimum, plus 1 */
-		const PlanGroupPackDev &G = D.gp;
-		uint64_t e0 = (uint64_t) code >> G.shift;
-		uint64_t e1 = (uint64_t) code & ((1ull << G.shift) - 1);
-
-		*k0 = e0 ? (int64_t) ((uint64_t) G.gmin[0] + e0 - 1)
-			: GG_PLAN_NULL_KEY;
-		*k1 = e1 ? (int64_t) ((uint64_t) G.gmin[1] + e1 - 1)
-			: GG_PLAN_NULL_KEY;
-	}
-	else if (D.ngroup == 2)
-	{
-		long long e0 = code / 512, e1 = code % 512;
-
-		*k0 = e0 == 256 ? GG_PLAN_NULL_KEY : e0;
-		*k1 = e1 == 256 ? GG_PLAN_NULL_KEY : e1;
-	}
-	else
-	{
-		*k0 = code;
-		*k1 = 0;
-	}
+	/* the decoder the device top-k shares (engine_internal.h) */
+	plan_keys_of(D.gp, D.ngroup, code, k0, k1);
 }
 
-/* 5. sort by decoded keys and materialize the arena */
+/* the value order entry E reads from a compacted row; false = SQL NULL.
+ * Group keys and MIN/MAX are int64, COUNT and SUM signed 128-bit */
+static bool
+plan_order_val(const PlanResolved *R, const PlanOrderEnt &E,
+	       const unsigned long long *row, i128 *v)
+{
+	if (E.kind == PL_ORD_I128)
+	{
+		*v = ((i128) (int64_t) row[2 + 2 * E.slot] << 64) |
+			(i128) row[1 + 2 * E.slot];
+		return true;
+	}
+	if (E.kind == PL_ORD_KEY)
+	{
+		int64_t k[2];
+
+		plan_keys_of(R->dev, (long long) row[0], &k[0], &k[1]);
+		*v = k[E.slot];
+		return k[E.slot] != GG_PLAN_NULL_KEY;
+	}
+	/* the order-encoded word, decoded as plan_write_arena decodes it */
+	unsigned long long e = E.kind == PL_ORD_MIN ? ~row[1 + 2 * E.slot]
+		: row[1 + 2 * E.slot];
+
+	*v = (int64_t) (e ^ 0x8000000000000000ull);
+	return row[1 + 2 * E.cnt] != 0;
+}
+
+/* THE order of a plan's groups (engine_abi.h gg_plan_order): true iff row a
+ * comes before row b.  The entries in turn, a NULL placed by nulls_first
+ * whatever the direction, then (key0, key1) ascending as raw int64, which
+ * is all there is with no entries.  Distinct groups never compare equal.
+ * The device top-k (plan_topk.hip) encodes this same order into its sort
+ * keys, and its survivors pass through here once more. */
+static bool
+plan_order_before(const PlanResolved *R, const unsigned long long *a,
+		  const unsigned long long *b)
+{
+	for (int o = 0; o < R->norder; o++)
+	{
+		const PlanOrderEnt &E = R->ord[o];
+		i128 va = 0, vb = 0;
+		bool ha = plan_order_val(R, E, a, &va);
+		bool hb = plan_order_val(R, E, b, &vb);
+
+		if (ha != hb)	/* one NULL: it goes first iff nulls_first */
+			return (!ha) == (E.nulls_first != 0);
+		if (ha && va != vb)
+			return (va < vb) != (E.desc != 0);
+	}
+	int64_t a0, a1, b0, b1;
+
+	plan_keys_of(R->dev, (long long) a[0], &a0, &a1);
+	plan_keys_of(R->dev, (long long) b[0], &b0, &b1);
+	return a0 != b0 ? a0 < b0 : a1 < b1;
+}
+
+/* 5. order the groups and materialize the arena: by decoded keys, or by
+ * the plan's order with its limit applied.  This host path serves every
+ * ordered plan the device top-k does not: several segments (it runs after
+ * plan_combine_segments; a top-k per segment ahead of the combine would be
+ * wrong, because a group's partial states live on several segments and no
+ * segment can rank it), limit > GG_PLAN_MAX_LIMIT, an order without a limit
+ * and tiny group sets.  After a device top-k, `rows` are its survivors and
+ * this is their final pass. */
 static gg_status
 plan_write_arena(const PlanResolved *R,
 		 const std::vector<unsigned long long> &rows, void *arena,
 		 size_t bytes, size_t *written)
 {
 	const int rowsz = plan_rowsz(R);
-	const size_t ng = rows.size() / rowsz;
+	size_t ng = rows.size() / rowsz;
 	std::vector<size_t> order(ng);
 
 	for (size_t i = 0; i < ng; i++)
 		order[i] = i;
-	std::sort(order.begin(), order.end(),
-		  [&](size_t a, size_t b)
-	{
-		int64_t a0, a1, b0, b1;
+	if (R->norder == 0 && R->limit == 0)
+		std::sort(order.begin(), order.end(),
+			  [&](size_t a, size_t b)
+		{
+			int64_t a0, a1, b0, b1;
 
-		plan_keys_of(R->dev, (long long) rows[a * rowsz], &a0, &a1);
-		plan_keys_of(R->dev, (long long) rows[b * rowsz], &b0, &b1);
-		return a0 != b0 ? a0 < b0 : a1 < b1;
-	});
+			plan_keys_of(R->dev, (long long) rows[a * rowsz], &a0,
+				     &a1);
+			plan_keys_of(R->dev, (long long) rows[b * rowsz], &b0,
+				     &b1);
+			return a0 != b0 ? a0 < b0 : a1 < b1;
+		});
+	else
+	{
+		auto before = [&](size_t a, size_t b)
+		{
+			return plan_order_before(R, &rows[a * rowsz],
+						 &rows[b * rowsz]);
+		};
+
+		if (R->limit > 0 && (uint64_t) R->limit < ng)
+		{
+			std::partial_sort(order.begin(),
+					  order.begin() + R->limit, order.end(),
+					  before);
+			ng = (size_t) R->limit;
+		}
+		else
+			std::sort(order.begin(), order.end(), before);
+	}
 
 	size_t need = 16 + (size_t) ng * (16 + 16 * (size_t) R->out_slots);
 
@@ -1096,6 +1293,90 @@ plan_write_arena(const PlanResolved *R,
 		}
 	}
 	*written = need;
+	return GG_OK;
+}
+
+/* a tile's sort keys must fit the device's LDS (160 KiB per workgroup on
+ * gfx950; four order entries take 148 KiB) */
+static bool
+plan_topk_fits(Engine &e, const PlanResolved *R)
+{
+	int lds = 0;
+
+	if (hipDeviceGetAttribute(&lds,
+				  hipDeviceAttributeMaxSharedMemoryPerBlock,
+				  e.cfg.device) != hipSuccess)
+		return false;
+	return plan_topk_lds_bytes(R->norder) <= (size_t) lds;
+}
+
+/* 4'. device top-k (plan_topk.hip): tournament rounds over the compacted
+ * rows until one tile is left, then only its first `limit` rows come to the
+ * host.  ng > limit, so the last tile's head holds `limit` real rows. */
+static gg_status
+plan_topk_device(Engine &e, Pipeline *p, const PlanResolved *R,
+		 const unsigned long long *dout, unsigned long long ng,
+		 std::vector<unsigned long long> &rows)
+{
+	const int rowsz = plan_rowsz(R);
+	const uint64_t limit = (uint64_t) R->limit;
+	PlanTopkDev K;
+
+	std::memset(&K, 0, sizeof(K));
+	K.rows = dout;
+	K.ng = ng;
+	K.rowsz = rowsz;
+	K.norder = R->norder;
+	K.limit = (int) limit;
+	K.ngroup = R->dev.ngroup;
+	K.gp = R->dev.gp;
+	for (int o = 0; o < R->norder; o++)
+		K.ord[o] = R->ord[o];
+
+	/* survivors of a round: its tiles x limit indices; the two buffers
+	 * alternate, the first round's output being the largest of each */
+	const uint64_t t0 = (ng + PL_TOPK_TILE - 1) / PL_TOPK_TILE;
+	const uint64_t t1 = (t0 * limit + PL_TOPK_TILE - 1) / PL_TOPK_TILE;
+	uint32_t *buf[2] = {
+		(uint32_t *) p->sget("plan.topk.a", t0 * limit * 4),
+		(uint32_t *) p->sget("plan.topk.b", t1 * limit * 4)};
+	unsigned long long *head = (unsigned long long *)
+		p->sget("plan.topk.out", limit * (size_t) rowsz * 8);
+
+	if (!buf[0] || !buf[1] || !head)
+		return fail(GG_ENOMEM, "plan top-k scratch");
+
+	Timed tm(e.stream);
+	const uint32_t *src = nullptr;
+	uint64_t n = ng;
+	int rounds = 0;
+
+	for (;;)
+	{
+		const uint64_t tiles = (n + PL_TOPK_TILE - 1) / PL_TOPK_TILE;
+		uint32_t *dst = buf[rounds & 1];
+
+		GG_HIP(launch_plan_topk_round(e.stream, K, src, n, dst));
+		rounds++;
+		src = dst;
+		if (tiles == 1)
+			break;
+		n = tiles * limit;
+	}
+	GG_HIP(launch_plan_topk_gather(e.stream, K, src, head));
+	{
+		double ms = tm.stop();
+		/* launches counts the tournament's rounds */
+		KernelStatAcc &st = p->stat("plan_topk");
+
+		st.launches += rounds;
+		st.total_ms += ms;
+		st.rows_in += (int64_t) ng;
+		st.rows_out += (int64_t) limit;
+	}
+	rows.resize((size_t) limit * rowsz);
+	GG_HIP(hipMemcpy(rows.data(), head, rows.size() * 8,
+			 hipMemcpyDeviceToHost));
 	return GG_OK;
 }
 
@@ -1162,15 +1443,38 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	if (R->dev.gp.packed)
 		GG_TRY(plan_group_pack(e, p, R));
 
-	unsigned long long *dout = nullptr;
+	unsigned long long *dout = nullptr, ng = 0;
 	std::vector<unsigned long long> rows;
+	const bool ordered = R->norder > 0 || R->limit > 0;
+	bool topk = false;
 
 	GG_TRY(plan_build_joins(e, p, R, ctr));
-	GG_TRY(plan_scan_groups(e, p, R, ctr, &dout, rows));
+	GG_TRY(plan_scan_groups(e, p, R, ctr, &dout, &ng));
+	if (ordered)
+	{
+		/* read once per execute, like GG_PLAN_BAKE */
+		const char *tk = getenv("GG_PLAN_TOPK");
+
+		/* ng > 8 leaves the small group sets, which the second-stage
+		 * bake wants whole on the host, to the host path */
+		topk = e.cfg.n_segments == 1 && R->limit > 0 &&
+			R->limit <= GG_PLAN_MAX_LIMIT &&
+			ng > (unsigned long long) R->limit && ng > 8 &&
+			ng < PL_TOPK_PAD && !(tk && !strcmp(tk, "host")) &&
+			plan_topk_fits(e, R);
+		p->stat(topk ? "path_plan_topk_device"
+			: "path_plan_topk_host").launches++;
+	}
+	if (topk)
+		GG_TRY(plan_topk_device(e, p, R, dout, ng, rows));
+	else
+		GG_TRY(plan_fetch_rows(R, dout, ng, rows));
 	if (e.cfg.n_segments > 1)
 		GG_TRY(plan_combine_segments(e, p, R, dout, rows));
 	GG_TRY(plan_write_arena(R, rows, arena, bytes, written));
-	plan_bake(e, p, R, rows);
+	/* the bake wants the whole group set; a top-k left only its head */
+	if (!topk)
+		plan_bake(e, p, R, rows);
 	return GG_OK;
 }
 

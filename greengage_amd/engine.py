@@ -72,6 +72,15 @@ class _PlanFilter(ctypes.Structure):
                 ("npreds", ctypes.c_int)]
 
 
+PLAN_MAX_ORDER = 4            # GG_PLAN_MAX_ORDER
+PLAN_MAX_LIMIT = 1024         # GG_PLAN_MAX_LIMIT (device top-k)
+
+
+class _PlanOrder(ctypes.Structure):
+    _fields_ = [("what", ctypes.c_int8), ("index", ctypes.c_int8),
+                ("desc", ctypes.c_int8), ("nulls_first", ctypes.c_int8)]
+
+
 class _PlanDesc(ctypes.Structure):
     _fields_ = [("scan", _PlanScan), ("joins", _PlanJoin * 2),
                 ("njoins", ctypes.c_int),
@@ -79,7 +88,10 @@ class _PlanDesc(ctypes.Structure):
                 ("ngroup", ctypes.c_int), ("aggs", _PlanAgg * 8),
                 ("naggs", ctypes.c_int), ("group_src", ctypes.c_int8 * 2),
                 ("filters", _PlanFilter * PLAN_MAX_FILTERS),
-                ("nfilters", ctypes.c_int)]
+                ("nfilters", ctypes.c_int),
+                ("order", _PlanOrder * PLAN_MAX_ORDER),
+                ("norder", ctypes.c_int), ("limit", I64),
+                ("est_groups", I64)]
 
 
 NEG_INF = -(1 << 63)          # one-sided range bounds
@@ -94,7 +106,7 @@ JOIN_LEFT, JOIN_ANTI = 2, 3
 
 
 def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
-                    aggs=()):
+                    aggs=(), order_by=(), limit=0, est_groups=0):
     """The gg_plan_desc (engine_abi.h) of a compositional plan and the
     aggregate kinds execute_plan decodes by: (desc, kinds).  Pure: calls
     neither the library nor a GPU.
@@ -134,6 +146,20 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
           descriptor's filters[]; more than PLAN_MAX_FILTERS distinct
           lists, or more than PLAN_MAX_FILTER_PREDS ranges in one, raise
           ValueError.
+    order_by: up to PLAN_MAX_ORDER entries
+          ("agg", a, "asc"|"desc"[, "nulls_first"|"nulls_last"]) |
+          ("key", g, "asc"|"desc"[, "nulls_first"|"nulls_last"])
+          ordering the groups by descriptor aggregate a (COUNT, SUM, MIN
+          or MAX; not AVG) or group column g.  Where the NULL placement
+          is omitted, PostgreSQL's default is filled in: NULLS LAST for
+          "asc", NULLS FIRST for "desc" (the ABI itself has no default).
+          Ties fall back to (key0, key1) ascending, so the order is
+          total.  Empty = the (key0, key1) order.
+    limit: 0 = every group; > 0 = at most that many, the first of the
+          order (up to PLAN_MAX_LIMIT they are selected on the device).
+    est_groups: 0 = the fixed group table; > 0 = an estimate of the
+          number of groups, which sizes the table and lets it grow.
+    The defaults leave the descriptor's tail zero.
     A group column, aggregate factor or filter `col` is a column name of
     the driving table, or a pair (join_index, name) for a column of
     that INNER or LEFT join's build table.
@@ -223,6 +249,21 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
             d.filters[k].preds[i].lo = lo
             d.filters[k].preds[i].hi = hi
             d.filters[k].src[i] = src
+    if len(order_by) > PLAN_MAX_ORDER:
+        raise ValueError(f"order_by holds at most {PLAN_MAX_ORDER} entries")
+    d.norder = len(order_by)
+    for o, ent in enumerate(order_by):
+        what, index, direction = ent[:3]
+        desc = {"asc": 0, "desc": 1}[direction]
+        # PostgreSQL: NULLS LAST for ASC, NULLS FIRST for DESC
+        nulls = ent[3] if len(ent) > 3 else ("nulls_first" if desc
+                                             else "nulls_last")
+        d.order[o].what = {"key": 0, "agg": 1}[what]
+        d.order[o].index = index
+        d.order[o].desc = desc
+        d.order[o].nulls_first = {"nulls_last": 0, "nulls_first": 1}[nulls]
+    d.limit = limit
+    d.est_groups = est_groups
     return d, kinds
 
 
@@ -290,6 +331,8 @@ def _load():
                                            ctypes.POINTER(I32)]
     lib.gg_engine_plan_desc_size.argtypes = []
     lib.gg_engine_plan_desc_size.restype = ctypes.c_size_t
+    lib.gg_engine_plan_topk_tile.argtypes = []
+    lib.gg_engine_plan_topk_tile.restype = ctypes.c_int
     lib.gg_engine_plan_group_bits.argtypes = [
         ctypes.POINTER(I64), ctypes.POINTER(I64),
         ctypes.POINTER(ctypes.c_int)]
@@ -435,6 +478,12 @@ def plan_group_bits(mn, mx):
     return rc, (bits[0], bits[1])
 
 
+def plan_topk_tile():
+    """Rows per tile of the device top-k's tournament
+    (gg_engine_plan_topk_tile): a constant of the library, no GPU needed."""
+    return lib().gg_engine_plan_topk_tile()
+
+
 class Engine:
     """One engine instance per process (= per GPU = per segment)."""
 
@@ -445,6 +494,7 @@ class Engine:
         self.n_segments = n_segments
         self.segment_id = segment_id
         self._plan_kinds = {}   # plan handle -> descriptor agg kinds
+        self._plan_limit = {}   # plan handle -> limit, where it has one
 
     def shutdown(self):
         _check(lib().gg_engine_shutdown(), "engine_shutdown")
@@ -555,24 +605,29 @@ class Engine:
 
     # ---- generalized pipeline descriptor (v2) ----
     def compile_plan(self, scan_table, preds=(), joins=(), group_cols=(),
-                     aggs=()):
+                     aggs=(), order_by=(), limit=0, est_groups=0):
         """Compile a compositional plan (engine_abi.h gg_plan_desc); the
         arguments are build_plan_desc's."""
         d, kinds = build_plan_desc(scan_table, preds, joins, group_cols,
-                                   aggs)
+                                   aggs, order_by, limit, est_groups)
         h = I32()
         _check(lib().gg_engine_compile_plan(ctypes.byref(d),
                                             ctypes.byref(h)), "compile_plan")
         self._plan_kinds[h.value] = kinds
+        if d.limit > 0:
+            self._plan_limit[h.value] = d.limit
         return h.value
 
     def execute_plan(self, p, max_groups=1 << 16):
-        """One (key0, key1, vals) per group; vals holds one entry per
-        descriptor aggregate: COUNT/SUM -> int, MIN/MAX -> int or None
+        """One (key0, key1, vals) per group, in arena order: by (key0,
+        key1), or as the plan's order_by / limit say.  vals holds one entry
+        per descriptor aggregate: COUNT/SUM -> int, MIN/MAX -> int or None
         (SQL NULL), AVG -> (sum, count) for avg_str."""
         kinds = self._plan_kinds.get(p)
         nslots_guess = 8 if kinds is None else max(
             8, sum(2 if k == AGG_AVG else 1 for k in kinds))
+        # a limited plan emits at most `limit` rows
+        max_groups = min(max_groups, self._plan_limit.get(p, max_groups))
         raw = self.execute_raw(
             p, 16 + max_groups * (16 + 16 * nslots_guess))
         ng = int.from_bytes(raw[0:8], "little", signed=True)

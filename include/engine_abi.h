@@ -646,6 +646,61 @@ typedef struct gg_plan_filter
 	int npreds;
 } gg_plan_filter;
 
+/* ORDER BY / LIMIT over the groups (Sort + Limit above the Agg: "top-k
+ * groups by an aggregate").
+ *
+ * Order.  Groups are ordered by order[0 .. norder), and ties are broken by
+ * (key0, key1) ascending, exactly as the arena is ordered without an order
+ * (raw int64, so GG_PLAN_NULL_KEY sorts first IN THE TIE-BREAK).  Groups are
+ * distinct, so this is a total order and the result, with or without a
+ * limit, is unique.  SQL promises no such thing; the engine does, so that a
+ * plan's result is the same on every path and for every segment count.
+ *   what = 0  group key `index`: compares the decoded key values as int64
+ *             (char1 reads as 0..255).  A NULL key is placed by
+ *             nulls_first, whatever `desc` says.
+ *   what = 1  descriptor aggregate `index`:
+ *             COUNT, SUM  compare as signed 128-bit values and are never
+ *                         NULL (a SUM with no input is 0, as in the arena)
+ *             MIN, MAX    compare the decoded int64; a group with N = 0 is
+ *                         NULL and is placed by nulls_first
+ *             AVG         GG_ENOTSUP at compile: comparing two AVGs exactly
+ *                         needs a 128 x 64-bit cross product
+ * nulls_first is explicit: the ABI has no default (PostgreSQL's is NULLS
+ * LAST for ASC and NULLS FIRST for DESC; a binding may fill that in).
+ *
+ * Limit.  limit > 0 emits at most that many groups, the first ones of the
+ * order; with norder == 0 that is LIMIT over the (key0, key1) order.  The
+ * arena keeps its layout: n_groups is the number of rows emitted,
+ * min(groups, limit), the rows come in the requested order, and the arena
+ * needs room for only that many.  limit == 0 means NO limit: SQL's
+ * LIMIT 0 (an empty result) is not expressible.  ngroup == 0 with any
+ * order or limit is accepted and yields its one row.
+ *
+ * With one segment, 0 < limit <= GG_PLAN_MAX_LIMIT and more groups than
+ * max(limit, 8), the first `limit` groups are selected on the device and
+ * only they are copied back; every other case (several segments, where a
+ * group's partial states live on several of them and no local top-k is the
+ * global one; a larger limit; an order without a limit; a handful of
+ * groups) copies the groups out and orders them on the host, with the same
+ * comparator.  GG_PLAN_TOPK=host in the environment forces the host path.
+ *
+ * Errors: limit < 0, norder outside [0, GG_PLAN_MAX_ORDER] or est_groups
+ * < 0 is GG_ENOTSUP, as is an AVG order key; `what` outside {0, 1}, a key
+ * index >= ngroup or an aggregate index >= naggs (or either < 0) is
+ * GG_EINVAL. */
+#define GG_PLAN_MAX_ORDER 4
+#define GG_PLAN_MAX_LIMIT 1024	/* device top-k; larger limits order on the
+				 * host */
+
+typedef struct gg_plan_order
+{
+	int8_t what;		/* 0 = group key, 1 = descriptor aggregate */
+	int8_t index;		/* group column g, or aggregate a (descriptor
+				 * order) */
+	int8_t desc;		/* 0 ASC, 1 DESC */
+	int8_t nulls_first;	/* 0 NULLS LAST, 1 NULLS FIRST */
+} gg_plan_order;
+
 typedef struct gg_plan_desc
 {
 	gg_plan_scan scan;	/* driving (probe-side) scan */
@@ -679,7 +734,10 @@ typedef struct gg_plan_desc
 	 * so an over-budget pair compiles and its first gg_engine_execute
 	 * returns GG_ENOTSUP (every segment alike; the shim falls back).
 	 * The host decodes (key0, key1) before sorting and writing the
-	 * arena.  Either way a two-column plan holds at most 2^18 groups. */
+	 * arena.  Either way, with est_groups == 0 the group table is fixed
+	 * (2^18 slots for one column, 2^19 for two) and a two-column plan
+	 * holds at most 2^18 groups; est_groups > 0 sizes the table from the
+	 * estimate and lets it grow (below). */
 	const char *group_cols[2];
 	int ngroup;
 	gg_plan_agg aggs[GG_PLAN_MAX_AGGS];
@@ -690,6 +748,30 @@ typedef struct gg_plan_desc
 	 * tail means what a descriptor without it meant */
 	gg_plan_filter filters[GG_PLAN_MAX_FILTERS];
 	int nfilters;
+	/* ORDER BY / LIMIT (gg_plan_order above) and the group-table
+	 * estimate; a zero-initialised tail again means what a descriptor
+	 * without it meant */
+	gg_plan_order order[GG_PLAN_MAX_ORDER];
+	int norder;		/* 0 = the (key0, key1) order */
+	int64_t limit;		/* 0 = no limit; > 0 = emit at most this many
+				 * groups */
+	/* 0 = the fixed group table and its cap.  > 0 = an estimate of the
+	 * number of groups in the style of Agg.numGroups: the table gets
+	 * max(the fixed size, next_pow2(2 * min(est_groups, driving rows)))
+	 * slots, and a scan that fills it is redone on a table four times
+	 * the size, up to next_pow2(2 * driving rows) slots, which cannot
+	 * fill.  The final size is remembered (tables are immutable), so
+	 * only a plan's first execute regrows; path_plan_group_grow counts
+	 * the regrows.  A table that, with its compacted output, does not
+	 * fit in free device memory is refused with GG_ENOTSUP before it is
+	 * allocated (the shim falls back).
+	 *
+	 * An underestimate is expensive by construction: once the table is
+	 * full, every further row of a new group probes ALL of it before
+	 * giving up, and the whole scan is then repeated.  That is what an
+	 * over-cap plan has always cost before failing; a good est_groups is
+	 * what avoids it. */
+	int64_t est_groups;
 } gg_plan_desc;
 
 #ifdef __cplusplus
@@ -704,7 +786,8 @@ _Static_assert(sizeof(gg_plan_agg) == 2 * sizeof(int) + 3 * sizeof(char *) + 8,
 
 /* result arena layout (little-endian):
  *   int64 n_groups; int32 naggs; int32 ngroup;
- *   then n_groups rows, sorted by (key0, key1) ascending:
+ *   then n_groups rows, sorted by (key0, key1) ascending, or ordered and
+ *   limited as the descriptor's order[] / limit say:
  *     int64 key0, int64 key1, then naggs x (uint64 lo, int64 hi)
  * naggs is the number of 16-byte result slots per row; slots follow
  * descriptor order:
@@ -731,6 +814,11 @@ gg_status gg_engine_compile_plan(const gg_plan_desc *desc, gg_pipeline *out);
 /* sizeof(gg_plan_desc) as this library was built: lets a binding check
  * its mirror of the layout without a GPU */
 size_t gg_engine_plan_desc_size(void);
+
+/* Rows per tile of the device top-k's tournament (a power of two, at least
+ * 2 * GG_PLAN_MAX_LIMIT): group counts around it are where the selection
+ * takes another round.  A constant of the build; needs no GPU. */
+int gg_engine_plan_topk_tile(void);
 
 /* Bit widths of a packed two-column group code (gg_plan_desc.group_cols)
  * from the two columns' signed value ranges [mn[g], mx[g]]; mn[g] >
