@@ -24,6 +24,7 @@ extern "C" size_t ZSTD_decompress(void *dst, size_t dstCap,
 extern "C" unsigned ZSTD_isError(size_t code);
 
 #include "engine_internal.h"
+#include "q1_pack.h"
 #include "../../include/gg_gen.h"
 
 namespace gg
@@ -237,12 +238,15 @@ extern "C" gg_status gg_engine_shutdown(void)
 	for (auto *t : e.tables)
 	{
 		if (t)
+		{
 			for (auto &c : t->cols)
 			{
 				(void) hipFree(c.dev);
 				if (c.nulls)
 					(void) hipFree(c.nulls);
 			}
+			t->free_q1pack();
+		}
 		delete t;
 	}
 	e.tables.clear();
@@ -1087,6 +1091,7 @@ extern "C" gg_status gg_engine_drop_table(gg_table h)
 		if (c.nulls)
 			(void) hipFree(c.nulls);
 	}
+	t->free_q1pack();
 	delete t;
 	e.tables[h] = nullptr;
 	return GG_OK;
@@ -1280,6 +1285,103 @@ gg_engine_register_synth(const char *table_name, uint64_t seed, int64_t sf,
 
 /* ---------------- pipelines ---------------- */
 
+/* GG_Q1_PACK=0 forces the wide Q1 scan (and keeps a compile from building
+ * a companion); read per call and per compile, like GG_Q1_NT */
+static bool q1_pack_enabled()
+{
+	const char *s = getenv("GG_Q1_PACK");
+
+	return !(s && s[0] == '0');
+}
+
+/*
+ * Plan-time build of the table's packed Q1 companion (q1_pack.h), once per
+ * table.  A table that lacks a Q1 column or is not eligible is remembered
+ * as such; a failed allocation leaves the decision open, clears the HIP
+ * error and lets Q1 run the wide kernel, so a table that only just fits in
+ * HBM keeps working.  The build's time goes to pipeline p's stats.
+ */
+static gg_status q1_pack_prepare(Engine &e, Table *t, Pipeline *p)
+{
+	static const struct
+	{
+		const char *name;
+		int width;
+	} want[7] = {{"qty", 8}, {"price", 8}, {"disc", 8}, {"tax", 8},
+		     {"shipdate", 4}, {"rflag", 1}, {"lstatus", 1}};
+	const void *col[7];
+	long long mn[5], mx[5];
+	Table::Q1Pack &k = t->q1pack;
+
+	if (k.state != 0)
+		return GG_OK;
+	for (int i = 0; i < 7; i++)
+	{
+		Table::Col *c = t->find(want[i].name);
+		int w = !c ? 0 : (c->type == GG_COL_INT32 ? 4
+				  : (c->type == GG_COL_CHAR1 ? 1 : 8));
+
+		/* one lane moves 4 rows with 16-byte accesses */
+		if (w != want[i].width || ((uintptr_t) c->dev & 15))
+		{
+			k.state = -1;
+			return GG_OK;
+		}
+		col[i] = c->dev;
+	}
+	if (t->nrows <= 0)
+	{
+		k.state = -1;
+		return GG_OK;
+	}
+	for (int i = 0; i < 5; i++)
+		GG_TRY(engine_col_minmax(e, col[i], want[i].width, t->nrows,
+					 &mn[i], &mx[i]));
+	Q1PackRanges r = {mn[0], mx[0], mn[1], mx[1], mn[2], mx[2],
+			  mn[3], mx[3], mn[4], mx[4]};
+
+	if (!q1_pack_eligible(t->nrows, r))
+	{
+		k.state = -1;
+		return GG_OK;
+	}
+	if (hipMalloc((void **) &k.w8, (size_t) t->nrows * 8) != hipSuccess ||
+	    hipMalloc((void **) &k.w4, (size_t) t->nrows * 4) != hipSuccess)
+	{
+		(void) hipGetLastError();
+		t->free_q1pack();
+		return GG_OK;
+	}
+	k.sd_base = (int32_t) r.sdmin;
+	k.row_bound = q1_pack_row_bound(r.pmax, r.tmax);
+	{
+		Timed tm(e.stream);
+		hipError_t he = launch_q1_pack_build(
+			e.stream, (const int32_t *) col[4],
+			(const uint8_t *) col[5], (const uint8_t *) col[6],
+			(const int64_t *) col[0], (const int64_t *) col[1],
+			(const int64_t *) col[2], (const int64_t *) col[3],
+			t->nrows, k.sd_base, k.w8, k.w4);
+		double ms = tm.stop();
+
+		if (he != hipSuccess)
+		{
+			t->free_q1pack();
+			return fail(GG_EGPU, "q1 pack build: %s",
+				    hipGetErrorString(he));
+		}
+		KernelStatAcc &st = p->stat("q1_pack_build");
+
+		st.launches++;
+		st.total_ms += ms;
+		st.rows_in += t->nrows;
+		st.rows_out += t->nrows;
+		st.hbm_bytes += t->nrows * (38 + 12);
+	}
+	k.state = 1;
+	return GG_OK;
+}
+
 extern "C" gg_status
 gg_engine_compile_pipeline(const gg_pipeline_desc *desc, gg_pipeline *out)
 {
@@ -1319,6 +1421,16 @@ gg_engine_compile_pipeline(const gg_pipeline_desc *desc, gg_pipeline *out)
 	Pipeline *p = new Pipeline();
 
 	p->desc = *desc;
+	if (desc->kind == GG_PIPE_Q1 && q1_pack_enabled())
+	{
+		gg_status st = q1_pack_prepare(e, get_table(desc->lineitem), p);
+
+		if (st != GG_OK)
+		{
+			delete p;
+			return st;
+		}
+	}
 	e.pipelines.push_back(p);
 	*out = (gg_pipeline) (e.pipelines.size() - 1);
 	return GG_OK;
@@ -1431,18 +1543,37 @@ static gg_status exec_q1(Pipeline *p, void *arena, size_t bytes,
 	if (!acc)
 		return fail(GG_ENOMEM, "q1 acc");
 	GG_HIP(hipMemsetAsync(acc, 0, sizeof(*acc), e.stream));
+	/* the packed companion when the table has one (built at compile),
+	 * else the wide columns; the stat row keeps its name on both paths */
+	const bool packed = li->q1pack.state == 1 && q1_pack_enabled();
+	uint32_t c = 0;
+
+	p->stat(packed ? "path_q1_packed" : "path_q1_wide").launches++;
+	if (packed && !q1_pack_cutoff(p->desc.cutoff_date, li->q1pack.sd_base,
+				      &c))
+	{
+		/* cutoff below every shipdate: no row passes, nothing to
+		 * launch; the zeroed accumulator is the empty result */
+	}
+	else
 	{
 		Timed tm(e.stream);
 
-		GG_HIP(launch_q1(e.stream, sd, rf, ls, q, pr, d, tx,
-				 li->nrows, p->desc.cutoff_date, acc));
+		if (packed)
+			GG_HIP(launch_q1_packed(e.stream, li->q1pack.w8,
+						li->q1pack.w4, li->nrows, c,
+						li->q1pack.row_bound, acc));
+		else
+			GG_HIP(launch_q1(e.stream, sd, rf, ls, q, pr, d, tx,
+					 li->nrows, p->desc.cutoff_date, acc));
 		double ms = tm.stop();
 		KernelStatAcc &st = p->stat("q1_agg");
 
 		st.launches++;
 		st.total_ms += ms;
 		st.rows_in += li->nrows;
-		st.hbm_bytes += li->nrows * 38;	/* SURVEY §8(d) */
+		/* 38 B/row wide, 12 B/row packed */
+		st.hbm_bytes += li->nrows * (packed ? 12 : 38);
 	}
 
 	/* combine partial states (2-stage agg: cdbgroup.c:1245 /

@@ -83,6 +83,28 @@ struct Table
 	};
 	std::vector<Col> cols;
 
+	/* Packed Q1 companion (q1_pack.h; DESIGN.md "Packed Q1 companion"):
+	 * a 12 B/row copy of the seven Q1 columns, built at most once per
+	 * table (registered columns are immutable) and shared by every Q1
+	 * pipeline over it.  state 0 = not decided yet, 1 = w8/w4 valid,
+	 * -1 = the table is not eligible (remembered, never re-checked). */
+	struct Q1Pack
+	{
+		int state = 0;
+		unsigned long long *w8 = nullptr;	/* nrows u64 */
+		uint32_t *w4 = nullptr;			/* nrows u32 */
+		int32_t sd_base = 0;			/* min(shipdate) */
+		uint64_t row_bound = 0;	/* q1_pack_row_bound(pmax, tmax) */
+	};
+	Q1Pack q1pack;
+
+	void free_q1pack()
+	{
+		(void) hipFree(q1pack.w8);
+		(void) hipFree(q1pack.w4);
+		q1pack = Q1Pack();
+	}
+
 	void *col(const char *n) const
 	{
 		for (auto &c : cols)
@@ -411,6 +433,17 @@ hipError_t launch_q1(hipStream_t s, const int32_t *shipdate,
 		     const int64_t *qty, const int64_t *price,
 		     const int64_t *disc, const int64_t *tax, int64_t n,
 		     int32_t cutoff, Q1DeviceAcc *acc);
+/* packed Q1 companion: build w8/w4 from the seven columns (every pointer
+ * 16-byte aligned), and scan them; c is q1_pack_cutoff's value */
+hipError_t launch_q1_pack_build(hipStream_t s, const int32_t *shipdate,
+				const uint8_t *rflag, const uint8_t *lstatus,
+				const int64_t *qty, const int64_t *price,
+				const int64_t *disc, const int64_t *tax,
+				int64_t n, int32_t sd_base,
+				unsigned long long *w8, uint32_t *w4);
+hipError_t launch_q1_packed(hipStream_t s, const unsigned long long *w8,
+			    const uint32_t *w4, int64_t n, uint32_t c,
+			    uint64_t row_bound, Q1DeviceAcc *acc);
 
 hipError_t launch_count_shard(hipStream_t s, int64_t row_lo, int64_t n,
 			      int nseg, int seg, int which_table,

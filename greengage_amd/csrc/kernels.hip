@@ -8,6 +8,8 @@
  *   k_q1_agg          execScan.c:110–214 + execHHashagg.c:905–1081 +
  *                     nodeAgg.c:393–860 (scan+filter+group agg, exact
  *                     scaled-int arithmetic)
+ *   k_q1_agg_packed   the same query over the 12 B/row companion that
+ *                     k_q1_pack_build writes once per table (q1_pack.h)
  *   k_build_* / k_probe_*  nodeHash.c:88–176/:905/:1002, nodeHashjoin.c:
  *                     78–510 (hash build/probe; open addressing instead
  *                     of chained buckets — GPU-native layout, same join
@@ -24,6 +26,7 @@
 #include "../../include/gg_gen.h"
 #include "../../include/gg_checksum.h"
 #include "engine_internal.h"
+#include "q1_pack.h"
 
 namespace gg
 {
@@ -212,6 +215,254 @@ launch_q1(hipStream_t s, const int32_t *shipdate, const uint8_t *rflag,
 		hipLaunchKernelGGL(k_q1_agg<false>, dim3(grid), dim3(THREADS),
 				   0, s, shipdate, rflag, lstatus, qty, price,
 				   disc, tax, n, cutoff, acc);
+	return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------ */
+/* Q1 over the packed companion (q1_pack.h): 12 B/row instead of 38    */
+/* ------------------------------------------------------------------ */
+
+typedef uint32_t q1_u32x4 __attribute__((ext_vector_type(4)));
+typedef int32_t q1_i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long q1_u64x2 __attribute__((ext_vector_type(2)));
+typedef long long q1_i64x2 __attribute__((ext_vector_type(2)));
+
+static_assert(Q1P_THREADS == THREADS, "q1_pack.h sizes the grid for THREADS");
+
+__device__ inline void
+q1_pack_row(int32_t sd, uint8_t rf, uint8_t ls, int64_t q, int64_t p,
+	    int64_t d, int64_t t, int32_t sd_base, unsigned long long *w8,
+	    uint32_t *w4)
+{
+	int fi = (rf == 'A') ? 0 : ((rf == 'N') ? 1 : ((rf == 'R') ? 2 : -1));
+	int si = (ls == 'F') ? 0 : ((ls == 'O') ? 1 : -1);
+	uint32_t code = (fi < 0 || si < 0) ? Q1P_BAD_CODE
+		: (uint32_t) (fi * 2 + si);
+
+	/* the host proved every value inside its field (q1_pack_eligible) */
+	*w8 = (unsigned long long) (uint32_t) p |
+		((unsigned long long) ((uint32_t) q & 0xFFFFu) << 32) |
+		((unsigned long long) ((uint32_t) d & 0xFFu) << 48) |
+		((unsigned long long) ((uint32_t) t & 0xFFu) << 56);
+	*w4 = (((uint32_t) sd - (uint32_t) sd_base) & 0xFFFFu) | (code << 16);
+}
+
+/* One lane packs 4 consecutive rows: eleven 16-byte-or-narrower loads of
+ * the seven columns, three 16-byte stores.  Rows past the last whole quad
+ * (n % 4) go one by one. */
+__global__ __launch_bounds__(THREADS)
+void k_q1_pack_build(const int32_t *__restrict__ shipdate,
+		     const uint8_t *__restrict__ rflag,
+		     const uint8_t *__restrict__ lstatus,
+		     const int64_t *__restrict__ qty,
+		     const int64_t *__restrict__ price,
+		     const int64_t *__restrict__ disc,
+		     const int64_t *__restrict__ tax,
+		     int64_t n, int32_t sd_base,
+		     unsigned long long *__restrict__ w8,
+		     uint32_t *__restrict__ w4)
+{
+	const int64_t nq = n / Q1P_ROWS;
+	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+	const int64_t gid = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+
+	for (int64_t qd = gid; qd < nq; qd += stride)
+	{
+		const int64_t i = qd * Q1P_ROWS;
+		q1_i32x4 sd = __builtin_nontemporal_load(
+			(const q1_i32x4 *) &shipdate[i]);
+		uint32_t rf = __builtin_nontemporal_load(
+			(const uint32_t *) &rflag[i]);
+		uint32_t ls = __builtin_nontemporal_load(
+			(const uint32_t *) &lstatus[i]);
+		q1_i64x2 q[2], p[2], d[2], t[2];
+		unsigned long long o8[Q1P_ROWS];
+		uint32_t o4[Q1P_ROWS];
+
+#pragma unroll
+		for (int h = 0; h < 2; h++)
+		{
+			q[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &qty[i + 2 * h]);
+			p[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &price[i + 2 * h]);
+			d[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &disc[i + 2 * h]);
+			t[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &tax[i + 2 * h]);
+		}
+#pragma unroll
+		for (int k = 0; k < Q1P_ROWS; k++)
+			q1_pack_row(sd[k], (uint8_t) (rf >> (8 * k)),
+				    (uint8_t) (ls >> (8 * k)), q[k >> 1][k & 1],
+				    p[k >> 1][k & 1], d[k >> 1][k & 1],
+				    t[k >> 1][k & 1], sd_base, &o8[k], &o4[k]);
+		*(q1_u64x2 *) &w8[i] = q1_u64x2{o8[0], o8[1]};
+		*(q1_u64x2 *) &w8[i + 2] = q1_u64x2{o8[2], o8[3]};
+		*(q1_u32x4 *) &w4[i] = q1_u32x4{o4[0], o4[1], o4[2], o4[3]};
+	}
+	if (gid == 0)
+		for (int64_t i = nq * Q1P_ROWS; i < n; i++)
+			q1_pack_row(shipdate[i], rflag[i], lstatus[i], qty[i],
+				    price[i], disc[i], tax[i], sd_base, &w8[i],
+				    &w4[i]);
+}
+
+hipError_t
+launch_q1_pack_build(hipStream_t s, const int32_t *shipdate,
+		     const uint8_t *rflag, const uint8_t *lstatus,
+		     const int64_t *qty, const int64_t *price,
+		     const int64_t *disc, const int64_t *tax, int64_t n,
+		     int32_t sd_base, unsigned long long *w8, uint32_t *w4)
+{
+	hipLaunchKernelGGL(k_q1_pack_build, dim3(grid_for(q1_pack_quads(n))),
+			   dim3(THREADS), 0, s, shipdate, rflag, lstatus, qty,
+			   price, disc, tax, n, sd_base, w8, w4);
+	return hipGetLastError();
+}
+
+/* one row's terms, exact: disc4 < 2^39, charge6 < 2^48 */
+struct Q1Terms
+{
+	unsigned long long cnt, q, p, d, disc4, charge6;
+};
+
+__device__ inline Q1Terms q1_unpack(unsigned long long w)
+{
+	Q1Terms r;
+
+	r.cnt = 1;
+	r.p = w & 0xFFFFFFFFull;
+	r.q = (w >> 32) & 0xFFFFull;
+	r.d = (w >> 48) & 0xFFull;
+	r.disc4 = r.p * (100ull - r.d);
+	r.charge6 = r.disc4 * (100ull + (w >> 56));
+	return r;
+}
+
+__device__ inline void q1_add6(unsigned long long *mine, uint32_t code,
+			       const Q1Terms &r)
+{
+	unsigned long long *g = &mine[code * Q1_FIELDS];
+
+	atomicAdd(&g[0], r.cnt);
+	atomicAdd(&g[1], r.q);
+	atomicAdd(&g[2], r.p);
+	atomicAdd(&g[3], r.d);
+	atomicAdd(&g[4], r.disc4);
+	atomicAdd(&g[5], r.charge6);
+}
+
+/*
+ * Scan of the companion.  Each lane takes 4 consecutive rows per
+ * iteration, so every load is 16 bytes and nontemporal: two of w8, one of
+ * w4.  Accumulation is k_q1_agg's: six LDS adds per passing row into
+ * replica lane % Q1_REPL.  At 12 B/row that still leaves the kernel at
+ * the HBM limit; combining a lane's 4 rows first and 64 replicas were
+ * measured and bought nothing (DESIGN.md "Packed Q1 companion").  A row
+ * with the bad-flag code sets the error bit only if it passes the date
+ * predicate, as in k_q1_agg.
+ */
+__global__ __launch_bounds__(THREADS, 2)
+void k_q1_agg_packed(const unsigned long long *__restrict__ w8,
+		     const uint32_t *__restrict__ w4, int64_t n, uint32_t c,
+		     Q1DeviceAcc *acc)
+{
+	__shared__ unsigned long long lds[Q1_REPL * Q1_STRIDE];
+
+	for (int i = threadIdx.x; i < Q1_REPL * Q1_STRIDE; i += blockDim.x)
+		lds[i] = 0;
+	__syncthreads();
+
+	unsigned long long *mine =
+		&lds[(threadIdx.x & (Q1_REPL - 1)) * Q1_STRIDE];
+	const int64_t nq = n / Q1P_ROWS;
+	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+	const int64_t gid = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	unsigned long long bad = 0;
+
+	for (int64_t qd = gid; qd < nq; qd += stride)
+	{
+		q1_u32x4 f = __builtin_nontemporal_load(
+			(const q1_u32x4 *) &w4[qd * Q1P_ROWS]);
+		q1_u64x2 a = __builtin_nontemporal_load(
+			(const q1_u64x2 *) &w8[qd * Q1P_ROWS]);
+		q1_u64x2 b = __builtin_nontemporal_load(
+			(const q1_u64x2 *) &w8[qd * Q1P_ROWS + 2]);
+		unsigned long long w[Q1P_ROWS] = { a[0], a[1], b[0], b[1] };
+
+#pragma unroll
+		for (int k = 0; k < Q1P_ROWS; k++)
+		{
+			uint32_t code = (f[k] >> 16) & 7u;
+
+			if ((f[k] & 0xFFFFu) > c)	/* l_shipdate <= cutoff */
+				continue;
+			if (code > 5u)
+				bad = 1;
+			else
+				q1_add6(mine, code, q1_unpack(w[k]));
+		}
+	}
+	/* the short tail (n % 4 rows, all of them when n < 4): scalar loads,
+	 * nothing past row n - 1 is read */
+	if (gid == 0)
+		for (int64_t i = nq * Q1P_ROWS; i < n; i++)
+		{
+			uint32_t f = w4[i];
+			uint32_t code = (f >> 16) & 7u;
+
+			if ((f & 0xFFFFu) > c)
+				continue;
+			if (code > 5u)
+				bad = 1;
+			else
+				q1_add6(mine, code, q1_unpack(w8[i]));
+		}
+	if (bad)
+		atomicOr(&acc->err, 1ull);
+	__syncthreads();
+
+	/* flush as k_q1_agg does: per-block sums fit u64 (the host sizes the
+	 * grid for it, q1_pack_grid), 128-bit carry at the global word */
+	for (int slot = threadIdx.x; slot < Q1_SLOTS; slot += blockDim.x)
+	{
+		const int g = slot / Q1_FIELDS;
+		const int fld = slot % Q1_FIELDS;
+		unsigned long long sum = 0;
+
+		if (fld > 5)
+			continue;
+		for (int r = 0; r < Q1_REPL; r++)
+			sum += lds[r * Q1_STRIDE + slot];
+		if (!sum)
+			continue;
+		if (fld < 4)
+			atomicAdd(&acc->v[g][fld], sum);
+		else
+		{
+			/* disc4 -> v[4], v[5]; charge6 -> v[6], v[7] */
+			const int lo = fld == 4 ? 4 : 6;
+			unsigned long long old = atomicAdd(&acc->v[g][lo], sum);
+
+			if (old + sum < old)
+				atomicAdd(&acc->v[g][lo + 1], 1ull);
+		}
+	}
+}
+
+hipError_t
+launch_q1_packed(hipStream_t s, const unsigned long long *w8,
+		 const uint32_t *w4, int64_t n, uint32_t c, uint64_t row_bound,
+		 Q1DeviceAcc *acc)
+{
+	/* GG_Q1_GRID forces the grid as it does for k_q1_agg; the floor
+	 * comes from this table's own maxima (q1_pack.h) */
+	const char *gs = getenv("GG_Q1_GRID");
+	int grid = (int) q1_pack_grid(n, gs ? atoi(gs) : 0, row_bound);
+
+	hipLaunchKernelGGL(k_q1_agg_packed, dim3(grid), dim3(THREADS), 0, s,
+			   w8, w4, n, c, acc);
 	return hipGetLastError();
 }
 
