@@ -7,6 +7,14 @@ there is NO CPU fallback: on a machine with a GPU, a missing or
 unloadable engine library raises immediately.
 """
 from .engine import (  # noqa: F401
+    ATOM_EQ,
+    ATOM_IS_NULL,
+    ATOM_LE,
+    ATOM_LT,
+    ATOM_NE,
+    ATOM_NOT_NULL,
+    ATOM_NOT_RANGE,
+    ATOM_RANGE,
     Engine,
     EngineError,
     JOIN_ANTI,
@@ -14,11 +22,15 @@ from .engine import (  # noqa: F401
     JOIN_LEFT,
     JOIN_SEMI,
     PGDate,
+    PLAN_MAX_ATOMS,
+    PLAN_MAX_CLAUSES,
     PLAN_MAX_FILTERS,
     PLAN_MAX_FILTER_PREDS,
     PLAN_MAX_LIMIT,
     PLAN_MAX_ORDER,
+    PLAN_MAX_WHERE_ATOMS,
     build_plan_desc,
+    build_plan_where,
     pgdate,
     plan_group_bits,
     plan_topk_tile,

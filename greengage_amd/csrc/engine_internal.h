@@ -753,6 +753,43 @@ static_assert(offsetof(PlanDev, fl) ==
 	      offsetof(PlanDev, gp) + sizeof(PlanGroupPackDev),
 	      "PlanFilterDev follows PlanGroupPackDev without padding");
 
+/* General WHERE clauses (engine_abi.h gg_plan_where), lowered: the atoms of
+ * one scope, clause after clause; clause c owns natoms[c] consecutive atoms.
+ * For scope 0 the first nscan clauses read the driving table alone (scan
+ * clauses, evaluated with the scan preds ahead of the joins), the others
+ * read some payload column (post-join clauses, evaluated once per row that
+ * survived preds and joins, ahead of the aggregate filters and the group
+ * code).  A build scope holds scan clauses only.
+ *
+ * The block is NOT a member of PlanDev.  The rule given at PlanPayloadDev
+ * (no field an existing plan reads may move) would allow appending it, but
+ * the interpreted kernel already carries PlanDev plus a PlFilters copy in
+ * its kernarg segment and a member here would be a third copy past the
+ * 4 KiB a launch may pass.  It reaches the interpreted kernel as an argument
+ * of its own (plan.hip PlWhere), the generated kernels as a trailing block
+ * directly behind PlanDev's bytes (plan_rtc.cpp GP_MEMBER), and k_plan_build
+ * as the last member of PlanBuildDev. */
+struct PlanAtomDev
+{
+	const void *col, *col2;			/* a, b (comparisons only) */
+	const uint8_t *nulls, *nulls2;
+	int64_t lo, hi;
+	int8_t kind;				/* gg_plan_atomkind */
+	int8_t src, src2;			/* column sources */
+	int8_t width, width2;
+};
+
+struct PlanWhereDev
+{
+	PlanAtomDev atoms[GG_PLAN_MAX_WHERE_ATOMS];
+	int8_t natoms[GG_PLAN_MAX_CLAUSES];
+	int8_t nclauses;
+	int8_t nscan;
+};
+
+static_assert(sizeof(PlanWhereDev) % 8 == 0 && alignof(PlanWhereDev) == 8,
+	      "PlanWhereDev follows PlanDev's bytes without padding");
+
 struct PlanBuildDev
 {
 	const void *key;
@@ -768,13 +805,16 @@ struct PlanBuildDev
 	uint32_t *idx;		/* INNER: row-index map (PlanPayloadDev.jidx) */
 	int kind;		/* gg_plan_joinkind */
 	unsigned long long *err;	/* plan error word (PL_ERR_DUP_KEY) */
+	PlanWhereDev wh;	/* scope 1+k clauses: a further build filter */
 };
 
 /* blocks of 256 threads for n rows, clamped to [1, 2048]: the grid of
  * every plan kernel, interpreted or generated */
 int pl_grid(int64_t n);
 hipError_t launch_plan_build(hipStream_t s, const PlanBuildDev &b);
-hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p);
+/* w = the plan's scope-0 WHERE clauses, nullptr for a plan without any */
+hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p,
+				const PlanWhereDev *w = nullptr);
 hipError_t launch_plan_compact(hipStream_t s,
 			       const unsigned long long *tkeys,
 			       const unsigned long long *tvals,
@@ -885,9 +925,11 @@ gg_status exec_plan(Pipeline *p, void *arena, size_t bytes,
 gg_status plan_rtc_compile(const PlanDev &D, bool has_gnull0,
 			   bool has_gnull1, std::shared_ptr<void> *out,
 			   const long long *bake = nullptr, int nbake = 0,
-			   bool fast = false);
+			   bool fast = false, const PlanWhereDev *W = nullptr);
+/* W must be what the kernel was compiled with (nullptr = no clauses) */
 gg_status plan_rtc_launch(hipStream_t s, const std::shared_ptr<void> &h,
-			  PlanDev P, int grid, int block);
+			  const PlanDev &P, int grid, int block,
+			  const PlanWhereDev *W = nullptr);
 
 /* engine_abi.cpp helpers shared with plan.cpp */
 Table *engine_table(gg_table h);

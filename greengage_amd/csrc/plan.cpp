@@ -86,6 +86,13 @@ struct PlanResolved
 	 * execute has settled it (0 = not yet) */
 	int64_t est_groups = 0;
 	uint64_t nslots = 0;
+	/* general WHERE clauses (gg_plan_where): the scope-0 clauses, scan
+	 * clauses first (build-scope clauses live in joins[k].bd.wh);
+	 * has_where = the plan has a clause of any scope, where0 = one of
+	 * scope 0, which is what the scan kernels are selected by */
+	PlanWhereDev wh = {};
+	bool has_where = false;
+	bool where0 = false;
 };
 
 static int coltype_width(gg_coltype t)
@@ -177,8 +184,181 @@ resolve_src(const gg_plan_desc *d, Table *scan, int src, int limit,
 	return GG_OK;
 }
 
-extern "C" gg_status
-gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
+extern "C" size_t
+gg_engine_plan_where_size(void)
+{
+	return sizeof(gg_plan_where);
+}
+
+static bool atom_compares(int kind)
+{
+	return kind >= GG_ATOM_LT && kind <= GG_ATOM_NE;
+}
+
+/* one side of an atom: the column `name` of source `src`, which in a build
+ * scope (bt != nullptr) must be 0 and names the build table itself */
+static gg_status
+resolve_atom_col(const gg_plan_desc *d, Table *scan, Table *bt, int c, int src,
+		 const char *name, Table::Col **out)
+{
+	Table *t = bt;
+
+	if (bt && src != 0)
+		return fail(GG_EINVAL, "plan: where clause %d: a build-scope "
+			    "atom names source %d (must be 0)", c, src);
+	if (!bt)
+		GG_TRY(resolve_src(d, scan, src, d->njoins,
+				   "atom src of where clause", c, &t));
+	*out = t->find(name ? name : "");
+	if (!*out)
+		return fail(GG_EINVAL, "plan: where clause %d: no column '%s' in "
+			    "table '%s'", c, name ? name : "(null)",
+			    t->name.c_str());
+	return GG_OK;
+}
+
+/* Lower the clauses of one scope (0 = the plan's WHERE, 1+k = join k's build
+ * filter) into W, scan clauses (every atom of source 0) first: the split is
+ * an implementation matter, the result is the conjunction either way.
+ * Adds each distinct (column, source) to `seen`. */
+static gg_status
+lower_where_scope(const gg_plan_desc *d, const gg_plan_where *w, Table *scan,
+		  int scope, PlanWhereDev *W,
+		  std::vector<std::pair<const void *, int>> &seen, int64_t *bytes)
+{
+	Table *bt = scope ? engine_table(d->joins[scope - 1].build.table)
+		: nullptr;
+	int na = 0;
+
+	std::memset(W, 0, sizeof(*W));
+	if (scope && !bt)
+		return fail(GG_EINVAL, "plan: bad build table (join %d)",
+			    scope - 1);
+	for (int pass = 0; pass < 2; pass++)
+	{
+		for (int c = 0; c < w->nclauses; c++)
+		{
+			const gg_plan_clause *C = &w->clauses[c];
+			bool post = false;
+
+			if (C->scope != scope)
+				continue;
+			for (int q = 0; q < C->natoms; q++)
+				if (C->atoms[q].src != 0 ||
+				    (atom_compares(C->atoms[q].kind) &&
+				     C->atoms[q].src2 != 0))
+					post = true;
+			if (scope)
+				post = false;	/* src != 0 is refused below */
+			if (post != (pass == 1))
+				continue;
+			for (int q = 0; q < C->natoms; q++)
+			{
+				const gg_plan_atom *A = &C->atoms[q];
+				PlanAtomDev &T = W->atoms[na++];
+				Table::Col *ca = nullptr, *cb = nullptr;
+
+				GG_TRY(resolve_atom_col(d, scan, bt, c, A->src, A->col,
+							&ca));
+				T.kind = A->kind;
+				T.col = ca->dev;
+				T.nulls = (const uint8_t *) ca->nulls;
+				T.width = (int8_t) coltype_width(ca->type);
+				T.src = A->src;
+				T.lo = A->lo;
+				T.hi = A->hi;
+				if (atom_compares(A->kind))
+				{
+					GG_TRY(resolve_atom_col(d, scan, bt, c, A->src2,
+								A->col2, &cb));
+					if ((ca->type == GG_COL_DEC64_S2) !=
+					    (cb->type == GG_COL_DEC64_S2))
+						return fail(GG_ENOTSUP, "plan: where "
+							    "clause %d compares a scaled "
+							    "decimal with an integer "
+							    "column (fall back to "
+							    "standard_ExecutorRun)", c);
+					T.col2 = cb->dev;
+					T.nulls2 = (const uint8_t *) cb->nulls;
+					T.width2 = (int8_t) coltype_width(cb->type);
+					T.src2 = A->src2;
+				}
+				for (int side = 0; side < (cb ? 2 : 1); side++)
+				{
+					const void *col = side ? T.col2 : T.col;
+					int src = side ? T.src2 : T.src;
+					bool dup = false;
+
+					for (auto &s : seen)
+						if (s.first == col && s.second == src)
+							dup = true;
+					if (dup)
+						continue;
+					seen.push_back({col, src});
+					*bytes += side ? T.width2 : T.width;
+				}
+			}
+			W->natoms[W->nclauses++] = (int8_t) C->natoms;
+		}
+		if (pass == 0)
+			W->nscan = W->nclauses;
+	}
+	return GG_OK;
+}
+
+/* the extension's own shape (engine_abi.h gg_plan_where, "Errors") */
+static gg_status
+check_where(const gg_plan_desc *d, const gg_plan_where *w)
+{
+	int total = 0;
+
+	if (w->nclauses < 0 || w->nclauses > GG_PLAN_MAX_CLAUSES)
+		return fail(GG_ENOTSUP, "plan: %d where clauses (fall back to "
+			    "standard_ExecutorRun)", w->nclauses);
+	for (int c = 0; c < w->nclauses; c++)
+	{
+		const gg_plan_clause *C = &w->clauses[c];
+
+		if (C->natoms > GG_PLAN_MAX_ATOMS)
+			return fail(GG_ENOTSUP, "plan: where clause %d has %d "
+				    "atoms (fall back to standard_ExecutorRun)", c,
+				    C->natoms);
+		if (C->natoms <= 0)
+			return fail(GG_EINVAL, "plan: where clause %d is an empty "
+				    "disjunction", c);
+		total += C->natoms;
+		for (int q = 0; q < C->natoms; q++)
+			if (C->atoms[q].kind < GG_ATOM_RANGE ||
+			    C->atoms[q].kind > GG_ATOM_NOT_NULL)
+				return fail(GG_ENOTSUP, "plan: where clause %d atom "
+					    "%d kind %d (fall back to "
+					    "standard_ExecutorRun)", c, q,
+					    C->atoms[q].kind);
+	}
+	if (total > GG_PLAN_MAX_WHERE_ATOMS)
+		return fail(GG_ENOTSUP, "plan: %d where atoms in all (fall back "
+			    "to standard_ExecutorRun)", total);
+	for (int c = 0; c < w->nclauses; c++)
+	{
+		const gg_plan_clause *C = &w->clauses[c];
+
+		if (C->scope < 0 || C->scope > d->njoins)
+			return fail(GG_EINVAL, "plan: where clause %d scope %d, "
+				    "the plan has %d joins", c, C->scope,
+				    d->njoins);
+		for (int q = 0; q < C->natoms; q++)
+			if (atom_compares(C->atoms[q].kind)
+			    ? !C->atoms[q].col2 : C->atoms[q].col2 != nullptr)
+				return fail(GG_EINVAL, "plan: where clause %d atom "
+					    "%d: col2 %s", c, q,
+					    C->atoms[q].col2 ? "on a non-comparison"
+					    : "missing on a comparison");
+	}
+	return GG_OK;
+}
+
+static gg_status
+plan_compile(const gg_plan_desc *d, const gg_plan_where *w, gg_pipeline *out)
 {
 	Engine &e = engine();
 
@@ -503,6 +683,27 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 	R->limit = d->limit;
 	R->est_groups = d->est_groups;
 
+	if (w)
+	{
+		/* each distinct (column, source) of the scope-0 clauses counts
+		 * once in pred_bytes_per_row, at its width; the builds' rows
+		 * are not part of that figure, with or without clauses */
+		std::vector<std::pair<const void *, int>> seen;
+		int64_t ignored = 0;
+
+		GG_TRY(check_where(d, w));
+		GG_TRY(lower_where_scope(d, w, scan, 0, &R->wh, seen,
+					 &R->pred_bytes_per_row));
+		R->where0 = R->wh.nclauses > 0;
+		for (int j = 0; j < d->njoins; j++)
+		{
+			seen.clear();
+			GG_TRY(lower_where_scope(d, w, scan, 1 + j,
+						 &R->joins[j].bd.wh, seen, &ignored));
+		}
+		R->has_where = true;
+	}
+
 	Pipeline *p = new Pipeline();
 
 	p->desc = gg_pipeline_desc{};
@@ -511,6 +712,21 @@ gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 	e.pipelines.push_back(p);
 	*out = (gg_pipeline) (e.pipelines.size() - 1);
 	return GG_OK;
+}
+
+extern "C" gg_status
+gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
+{
+	return plan_compile(d, nullptr, out);
+}
+
+extern "C" gg_status
+gg_engine_compile_plan_where(const gg_plan_desc *d, const gg_plan_where *w,
+			     gg_pipeline *out)
+{
+	/* no clauses: gg_engine_compile_plan exactly.  A count outside its
+	 * bounds is refused once the descriptor itself has been checked */
+	return plan_compile(d, w && w->nclauses != 0 ? w : nullptr, out);
 }
 
 static uint64_t next_pow2_pl(uint64_t v)
@@ -549,10 +765,12 @@ plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
 {
 	const PlanDev &D = R->dev;
 
+	const PlanWhereDev *W = R->where0 ? &R->wh : nullptr;
+
 	if (k)
-		GG_TRY(plan_rtc_launch(e.stream, k, D, pl_grid(D.n), 256));
+		GG_TRY(plan_rtc_launch(e.stream, k, D, pl_grid(D.n), 256, W));
 	else
-		GG_HIP(launch_plan_scan_agg(e.stream, D));
+		GG_HIP(launch_plan_scan_agg(e.stream, D, W));
 	if (tm)
 	{
 		double ms = tm->stop();
@@ -584,7 +802,9 @@ plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
  * extension by a LEFT join does the same and no
  * more (a NULL-extended factor is skipped by the
  * strict transition), so it needs no new
- * arithmetic either. */
+ * arithmetic either.  A general WHERE clause
+ * (gg_plan_where) only removes rows, so the
+ * bounds stay valid under it as well. */
 static bool
 plan_fast_tier_provable(Engine &e, const PlanResolved *R)
 {
@@ -946,7 +1166,8 @@ plan_scan_groups(Engine &e, Pipeline *p, PlanResolved *R,
 			 * resolved; NULL presence and widths are baked */
 			gg_status rs = plan_rtc_compile(
 				R->dev, R->dev.gnulls[0] != nullptr,
-				R->dev.gnulls[1] != nullptr, &R->rtc);
+				R->dev.gnulls[1] != nullptr, &R->rtc, nullptr, 0,
+				false, R->where0 ? &R->wh : nullptr);
 
 			R->rtc_tried = true;
 			p->stat(rs == GG_OK ? "path_plan_rtc"
@@ -1409,7 +1630,8 @@ plan_bake(Engine &e, Pipeline *p, PlanResolved *R,
 		gg_status rs = plan_rtc_compile(
 			R->dev, R->dev.gnulls[0] != nullptr,
 			R->dev.gnulls[1] != nullptr, &R->rtc_baked,
-			codes.data(), (int) ng, fastok);
+			codes.data(), (int) ng, fastok,
+			R->where0 ? &R->wh : nullptr);
 
 		R->bake_tried = true;
 		if (rs == GG_OK)
@@ -1448,6 +1670,8 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	const bool ordered = R->norder > 0 || R->limit > 0;
 	bool topk = false;
 
+	if (R->has_where)
+		p->stat("path_plan_where").launches++;
 	GG_TRY(plan_build_joins(e, p, R, ctr));
 	GG_TRY(plan_scan_groups(e, p, R, ctr, &dout, &ng));
 	if (ordered)

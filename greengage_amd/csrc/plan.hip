@@ -29,6 +29,13 @@
  *                 strict transition: per-aggregate range conjunctions
  *                 over driving or payload columns, evaluated once per
  *                 surviving row; they never touch the groups
+ *   where clauses engine_abi.h gg_plan_where: a qual in conjunctive normal
+ *                 form (ExecEvalAnd over ExecEvalOr over atoms; ExecEvalNot
+ *                 only inside the atoms), atoms being ranges, negated ranges,
+ *                 column comparisons, IS [NOT] NULL (ExecEvalNullTest) and
+ *                 IN-lists as equalities (ExecEvalScalarArrayOp).  An atom
+ *                 is true or not true, a comparison over NULL not true;
+ *                 ExecQual drops the row whose qual is not true
  *   agg exprs     products with (100±col) under numeric.c:1735 mul_var
  *                 scale addition (scaled-int exact arithmetic)
  *
@@ -139,6 +146,120 @@ pl_preds_pass4(const PlanPredDev *preds, int npreds, int64_t i, int64_t S,
 	}
 }
 
+/* ---- general WHERE clauses (engine_abi.h gg_plan_where) ---------------
+ * One atom on loaded values: a, b the two columns widened to int64, na / nb
+ * "the column is SQL NULL".  A comparison over a NULL is not true; IS_NULL
+ * is true exactly then (ExecEvalNullTest).  True comparisons, never a
+ * subtraction.  The kind is uniform over the wave, so the switch is a
+ * scalar branch; the row's own work is branch-free. */
+__device__ static inline bool
+pl_atom_true(int kind, int64_t a, int64_t b, int64_t lo, int64_t hi, bool na,
+	     bool nb)
+{
+	switch (kind)
+	{
+		case GG_ATOM_RANGE:
+			return !na & (a >= lo) & (a < hi);
+		case GG_ATOM_NOT_RANGE:
+			return !na & ((a < lo) | (a >= hi));
+		case GG_ATOM_LT:
+			return !(na | nb) & (a < b);
+		case GG_ATOM_LE:
+			return !(na | nb) & (a <= b);
+		case GG_ATOM_EQ:
+			return !(na | nb) & (a == b);
+		case GG_ATOM_NE:
+			return !(na | nb) & (a != b);
+		case GG_ATOM_IS_NULL:
+			return na;
+		default:	/* GG_ATOM_NOT_NULL */
+			return !na;
+	}
+}
+
+/* the scan clauses (every atom of source 0) of W at row i: OR within a
+ * clause, AND across clauses (ExecEvalOr / ExecEvalAnd on true / not-true) */
+__device__ static inline bool
+pl_where_scan(const PlanWhereDev &W, int64_t i)
+{
+	bool ok = true;
+	int q = 0;
+
+	for (int c = 0; c < W.nscan; c++)
+	{
+		bool t = false;
+
+		for (const int e = q + W.natoms[c]; q < e; q++)
+		{
+			const PlanAtomDev &A = W.atoms[q];
+			int64_t a = 0, b = 0;
+			bool nb = false;
+			const bool na = A.nulls && A.nulls[i];
+
+			if (A.kind < GG_ATOM_IS_NULL)
+				a = pl_ld<0>(A.col, A.width, i);
+			if (A.col2)
+			{
+				b = pl_ld<0>(A.col2, A.width2, i);
+				nb = A.nulls2 && A.nulls2[i];
+			}
+			t |= pl_atom_true(A.kind, a, b, A.lo, A.hi, na, nb);
+		}
+		ok &= t;
+	}
+	return ok;
+}
+
+/* ... and for the 4 strided rows, under pl_preds_pass4's rule: every atom
+ * column is loaded unconditionally for the four rows, no per-row short
+ * circuit.  An atom over the column its predecessor in the clause read (an
+ * IN-list) reuses the loaded values. */
+__device__ static inline void
+pl_where_scan4(const PlanWhereDev &W, int64_t i, int64_t S, bool ok[4])
+{
+	int q = 0;
+
+	for (int c = 0; c < W.nscan; c++)
+	{
+		bool t[4] = {false, false, false, false};
+		const void *last = nullptr;
+		int64_t a[4] = {0, 0, 0, 0};
+		bool na[4] = {false, false, false, false};
+
+		for (const int e = q + W.natoms[c]; q < e; q++)
+		{
+			const PlanAtomDev &A = W.atoms[q];
+			int64_t b[4] = {0, 0, 0, 0};
+			bool nb[4] = {false, false, false, false};
+
+			if (A.col != last)
+			{
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+				{
+					a[j] = pl_ld<0>(A.col, A.width, i + j * S);
+					na[j] = A.nulls && A.nulls[i + j * S];
+				}
+				last = A.col;
+			}
+			if (A.col2)
+#pragma unroll
+				for (int j = 0; j < 4; j++)
+				{
+					b[j] = pl_ld<0>(A.col2, A.width2, i + j * S);
+					nb[j] = A.nulls2 && A.nulls2[i + j * S];
+				}
+#pragma unroll
+			for (int j = 0; j < 4; j++)
+				t[j] |= pl_atom_true(A.kind, a[j], b[j], A.lo, A.hi,
+						     na[j], nb[j]);
+		}
+#pragma unroll
+		for (int j = 0; j < 4; j++)
+			ok[j] &= t[j];
+	}
+}
+
 /* ---- join build ------------------------------------------------------
  * INNER = 0: today's membership set (bitmap or hash set), duplicates
  * welcome.  INNER = 1: key -> build-row-index map for a unique-keyed
@@ -156,6 +277,9 @@ void k_plan_build(PlanBuildDev B)
 	     i < B.n; i += stride)
 	{
 		if (!pl_preds_pass<0>(B.preds, B.npreds, i))
+			continue;
+		/* scope 1+k clauses: a further filter of the build rows */
+		if (B.wh.nscan && !pl_where_scan(B.wh, i))
 			continue;
 		if (B.knulls && B.knulls[i])
 			continue;	/* NULL build key never matches */
@@ -342,6 +466,71 @@ pl_ix(const PlRow<PL> &R, int src, int64_t i)
 		return src == 0 ? i : (int64_t) (src == 1 ? R.r[0] : R.r[1]);
 	else
 		return i;
+}
+
+/* A plan with scope-0 WHERE clauses: the kernel then gets them as one more
+ * argument of its own, for the reason given at PlFilters below: no new
+ * read of P.  The argument is a parameter pack, empty for a plan without
+ * clauses, whose kernel so keeps its argument block to the byte and
+ * compiles to the code it always had. */
+struct PlWhere
+{
+	PlanWhereDev w;
+};
+
+__device__ static inline const PlanWhereDev &pl_where_arg(const PlWhere &W)
+{
+	return W.w;
+}
+
+/* the post-join clauses of W, once per row that survived preds and joins.
+ * Columns are read at the row their source names.  The test for a
+ * NULL-extended source (pl_src_null, r == PL_NOROW) comes AHEAD of every
+ * address computation, the NULL-flag load included: such a column is NULL
+ * and neither its flag nor its value is loaded. */
+template <int PL>
+__device__ static inline bool
+pl_where_post(const PlanWhereDev &W, int64_t i, const PlRow<PL> &R)
+{
+	int q = 0;
+
+	for (int c = 0; c < W.nscan; c++)
+		q += W.natoms[c];
+	for (int c = W.nscan; c < W.nclauses; c++)
+	{
+		bool t = false;
+
+		for (const int e = q + W.natoms[c]; q < e; q++)
+		{
+			const PlanAtomDev &A = W.atoms[q];
+			int64_t a = 0, b = 0;
+			bool na = true, nb = false;
+
+			if (!pl_src_null<PL>(R, A.src))
+			{
+				const int64_t ia = pl_ix<PL>(R, A.src, i);
+
+				na = A.nulls && A.nulls[ia];
+				if (A.kind < GG_ATOM_IS_NULL)
+					a = pl_ld<0>(A.col, A.width, ia);
+			}
+			if (A.col2)
+			{
+				nb = true;
+				if (!pl_src_null<PL>(R, A.src2))
+				{
+					const int64_t ib = pl_ix<PL>(R, A.src2, i);
+
+					nb = A.nulls2 && A.nulls2[ib];
+					b = pl_ld<0>(A.col2, A.width2, ib);
+				}
+			}
+			t |= pl_atom_true(A.kind, a, b, A.lo, A.hi, na, nb);
+		}
+		if (!t)
+			return false;
+	}
+	return true;
 }
 
 /* the same walk for a plan with an INNER join: joins run in descriptor
@@ -822,10 +1011,12 @@ pl_fold_flush(int kind, unsigned long long *dst, Rep rep)
 		pl_atomic_add128(dst, lo, hi);
 }
 
-template <int NT, int MM, int PL, int GP, int FL>
+template <int NT, int MM, int PL, int GP, int FL, class... Where>
 __global__ __launch_bounds__(PL_THREADS, 4)
-void k_plan_scan_agg(PlanDev P, PlFilters<FL> F)
+void k_plan_scan_agg(PlanDev P, PlFilters<FL> F, Where... W)
 {
+	constexpr bool WH = sizeof...(Where) != 0;
+
 	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
 
 	/* Both group modes scan the same way: 4-way strided rows with
@@ -846,6 +1037,9 @@ void k_plan_scan_agg(PlanDev P, PlFilters<FL> F)
 
 			if (!pl_row_joins<PL>(P, i, R))
 				return;
+			if constexpr (WH)
+				if (!pl_where_post<PL>(pl_where_arg(W...), i, R))
+					return;
 			unsigned fm = 0;
 
 			if constexpr (FL)
@@ -860,13 +1054,20 @@ void k_plan_scan_agg(PlanDev P, PlFilters<FL> F)
 			bool ok[4];
 
 			pl_preds_pass4<NT>(P.preds, P.npreds, i, stride, ok);
+			if constexpr (WH)
+				pl_where_scan4(pl_where_arg(W...), i, stride, ok);
 			for (int j = 0; j < 4; j++)
 				if (ok[j])
 					row(i + j * stride);
 		}
 		for (; i < P.n; i += stride)
+		{
+			if constexpr (WH)
+				if (!pl_where_scan(pl_where_arg(W...), i))
+					continue;
 			if (pl_preds_pass<NT>(P.preds, P.npreds, i))
 				row(i);
+		}
 		for (int a = 0; a < P.naggs; a++)
 		{
 			if (MM && P.aggs[a].kind >= 3)
@@ -930,6 +1131,9 @@ void k_plan_scan_agg(PlanDev P, PlFilters<FL> F)
 
 		if (!pl_row_joins<PL>(P, i, R))
 			return;
+		if constexpr (WH)
+			if (!pl_where_post<PL>(pl_where_arg(W...), i, R))
+				return;
 		unsigned fm = 0;
 
 		if constexpr (FL)
@@ -991,13 +1195,20 @@ void k_plan_scan_agg(PlanDev P, PlFilters<FL> F)
 		bool ok[4];
 
 		pl_preds_pass4<NT>(P.preds, P.npreds, i, stride, ok);
+		if constexpr (WH)
+			pl_where_scan4(pl_where_arg(W...), i, stride, ok);
 		for (int j = 0; j < 4; j++)
 			if (ok[j])
 				row(i + j * stride);
 	}
 	for (; i < P.n; i += stride)
+	{
+		if constexpr (WH)
+			if (!pl_where_scan(pl_where_arg(W...), i))
+				continue;
 		if (pl_preds_pass<NT>(P.preds, P.npreds, i))
 			row(i);
+	}
 
 	/* flush the block's LDS groups into the global table */
 	__syncthreads();
@@ -1044,6 +1255,29 @@ static void pl_launch(hipStream_t s, const PlanDev &p)
 			   pl_filters_arg<FL>(p));
 }
 
+/* A plan with scope-0 WHERE clauses.  The interpreted kernel is the
+ * fallback tier (such a plan normally runs its generated kernel), so the
+ * clauses buy two instantiations, not another 48: they imply NT = 0 and
+ * the most general value of every flag whose general form also serves the
+ * plans of the lesser ones: MM = 1 (the MIN/MAX branches are behind the
+ * accumulator's kind), PL = 2 (pl_joins_outer walks all four join kinds and
+ * none) and FL = 1 (an empty `used` mask evaluates nothing).  GP stays a
+ * flag: the packed code is not a superset of the others. */
+static_assert(sizeof(PlanDev) + sizeof(PlFilters<1>) + sizeof(PlWhere) <=
+	      4096, "the interpreted kernel's arguments fit a kernarg segment");
+
+template <int GP>
+static void pl_launch_where(hipStream_t s, const PlanDev &p,
+			    const PlanWhereDev &w)
+{
+	PlWhere W;
+
+	W.w = w;
+	hipLaunchKernelGGL((k_plan_scan_agg<0, 1, 2, GP, 1, PlWhere>),
+			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p,
+			   pl_filters_arg<1>(p), W);
+}
+
 typedef void (*PlLaunchFn)(hipStream_t, const PlanDev &);
 struct PlFlags
 {
@@ -1087,8 +1321,18 @@ static_assert(pl_pinned<0, 0, 0, 0, 0>() && pl_pinned<1, 1, 2, 1, 1>() &&
 	      pl_pinned<0, 0, 0, 1, 0>() && pl_pinned<0, 0, 0, 0, 1>(),
 	      "k_plan_scan_agg launcher table: decode and encode disagree");
 
-hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p)
+hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p,
+				const PlanWhereDev *w)
 {
+	if (w)
+	{
+		if (p.ngroup == 2 && p.gp.packed)
+			pl_launch_where<1>(s, p, *w);
+		else
+			pl_launch_where<0>(s, p, *w);
+		return hipGetLastError();
+	}
+
 	const char *nt = getenv("GG_PLAN_NT");
 	bool mm = false;
 	/* 1: the row carries build-row indices (an INNER join); 2: a LEFT or

@@ -51,7 +51,10 @@ struct PlanRtc
  * always had (plan_rtc_launch passes that many bytes).  A plan that
  * references an aggregate filter gets both trailing blocks, `gp` and the
  * PlanFilterDev after it, through the same two macros, so this text and
- * with it every other plan's program stays byte for byte what it was */
+ * with it every other plan's program stays byte for byte what it was.  A
+ * plan with scope-0 WHERE clauses gets a third block, PlanWhereDev `wh`,
+ * behind those two: it is no member of the host's PlanDev (see there), the
+ * launch lays it directly behind PlanDev's bytes */
 static const char *STRUCT_DEFS = R"GG(
 typedef long long int64_t;
 typedef unsigned long long uint64_t;
@@ -306,7 +309,25 @@ struct Gen
 	bool nt;		/* nontemporal scan loads */
 	bool payload;		/* the plan holds an INNER or LEFT join: rows
 				 * carry the build-row indices r0, r1 */
+	const PlanWhereDev *W;	/* scope-0 WHERE clauses, or nullptr */
 };
+
+/* what a launch passes for a plan with WHERE clauses */
+struct PlanDevWhere
+{
+	PlanDev p;
+	PlanWhereDev wh;
+};
+
+static_assert(offsetof(PlanDevWhere, wh) == sizeof(PlanDev) &&
+	      sizeof(PlanDevWhere) == sizeof(PlanDev) + sizeof(PlanWhereDev),
+	      "PlanWhereDev follows PlanDev's bytes without padding");
+
+/* the plan has clauses evaluated after the joins */
+static bool where_post(const Gen &G)
+{
+	return G.W && G.W->nclauses > G.W->nscan;
+}
 
 /* Source `src` is a LEFT join.  Its index r<j> is 0xFFFFFFFF on a row the
  * join NULL-extended, and no load may be issued with it: the row carries
@@ -345,9 +366,9 @@ static bool filter_args(const PlanDev &D)
 	return D.fl.used != 0;
 }
 
-static size_t plan_arg_bytes(const PlanDev &D)
+static size_t plan_arg_bytes(const PlanDev &D, const PlanWhereDev *W)
 {
-	return filter_args(D) ? sizeof(PlanDev)
+	return W ? sizeof(PlanDevWhere) : filter_args(D) ? sizeof(PlanDev)
 		: packed_args(D) ? offsetof(PlanDev, fl) : offsetof(PlanDev, gp);
 }
 
@@ -363,7 +384,20 @@ static void emit_prelude(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
 
-	s += filter_args(D)
+	s += G.W
+		? "#define GP_STRUCT struct PlanGroupPackDev "
+		  "{ int packed; int shift; int64_t gmin[2]; }; "
+		  "struct PlanFilterDev { PlanPredDev preds[4][4]; "
+		  "int8_t psrc[4][4]; int8_t npreds[4]; int8_t afilt[8]; "
+		  "int used; }; "
+		  "struct PlanAtomDev { const void *col, *col2; "
+		  "const uint8_t *nulls, *nulls2; int64_t lo, hi; int8_t kind; "
+		  "int8_t src, src2; int8_t width, width2; }; "
+		  "struct PlanWhereDev { PlanAtomDev atoms[16]; "
+		  "int8_t natoms[8]; int8_t nclauses; int8_t nscan; };\n"
+		  "#define GP_MEMBER PlanGroupPackDev gp; PlanFilterDev fl; "
+		  "PlanWhereDev wh;\n"
+		: filter_args(D)
 		? "#define GP_STRUCT struct PlanGroupPackDev "
 		  "{ int packed; int shift; int64_t gmin[2]; }; "
 		  "struct PlanFilterDev { PlanPredDev preds[4][4]; "
@@ -383,7 +417,7 @@ static void emit_prelude(std::string &s, const Gen &G)
 		 "static_assert(sizeof(PlanAggDev) == %zu, \"layout\");\n"
 		 "static_assert(sizeof(PlanDev) == %zu, \"layout\");\n",
 		 sizeof(PlanPredDev), sizeof(PlanJoinDev), sizeof(PlanAggDev),
-		 plan_arg_bytes(D));
+		 plan_arg_bytes(D, G.W));
 	s += fmt("static_assert(__builtin_offsetof(PlanDev, joins) == %zu, \"layout\");\n"
 		 "static_assert(__builtin_offsetof(PlanDev, tkeys) == %zu, \"layout\");\n"
 		 "static_assert(__builtin_offsetof(PlanDev, err) == %zu, \"layout\");\n"
@@ -397,13 +431,24 @@ static void emit_prelude(std::string &s, const Gen &G)
 		 sizeof(PlanPayloadDev), offsetof(PlanDev, pl),
 		 offsetof(PlanPayloadDev, jkind),
 		 offsetof(PlanPayloadDev, asrc));
-	if (packed_args(D) || filter_args(D))
+	if (packed_args(D) || filter_args(D) || G.W)
 		s += fmt("static_assert(sizeof(PlanGroupPackDev) == %zu, \"layout\");\n"
 			 "static_assert(__builtin_offsetof(PlanDev, gp) == %zu, \"layout\");\n"
 			 "static_assert(__builtin_offsetof(PlanGroupPackDev, gmin) == %zu, \"layout\");\n",
 			 sizeof(PlanGroupPackDev), offsetof(PlanDev, gp),
 			 offsetof(PlanGroupPackDev, gmin));
-	if (filter_args(D))
+	if (G.W)
+		s += fmt("static_assert(sizeof(PlanAtomDev) == %zu, \"layout\");\n"
+			 "static_assert(sizeof(PlanWhereDev) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanDev, wh) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanAtomDev, lo) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanAtomDev, kind) == %zu, \"layout\");\n"
+			 "static_assert(__builtin_offsetof(PlanWhereDev, natoms) == %zu, \"layout\");\n",
+			 sizeof(PlanAtomDev), sizeof(PlanWhereDev),
+			 offsetof(PlanDevWhere, wh), offsetof(PlanAtomDev, lo),
+			 offsetof(PlanAtomDev, kind),
+			 offsetof(PlanWhereDev, natoms));
+	if (filter_args(D) || G.W)
 		s += fmt("static_assert(sizeof(PlanFilterDev) == %zu, \"layout\");\n"
 			 "static_assert(__builtin_offsetof(PlanDev, fl) == %zu, \"layout\");\n"
 			 "static_assert(__builtin_offsetof(PlanFilterDev, psrc) == %zu, \"layout\");\n"
@@ -550,6 +595,107 @@ static void emit_join(std::string &s, const PlanDev &D, int j)
 		s += "\t\t}\n";
 }
 
+/* ---- general WHERE clauses (engine_abi.h gg_plan_where) ----
+ * "Column x of source src is SQL NULL" as program text, "" = never: by its
+ * own flag array `nptr`, or, for a LEFT source, on a NULL-extended row.
+ * The partner flag h<j> comes first, and `||` / `&&` keep the flag load
+ * behind it. */
+static std::string atom_isnull(const PlanDev &D, int src, bool has_nulls,
+			       const std::string &nptr)
+{
+	const std::string f = has_nulls ? nptr + "[" + ix_of(src) + "]" : "";
+
+	if (left_src(D, src))
+		return f.empty() ? fmt("!h%d", src - 1)
+			: fmt("(!h%d || ", src - 1) + f + ")";
+	return f;
+}
+
+static std::string atom_notnull(const PlanDev &D, int src, bool has_nulls,
+				const std::string &nptr)
+{
+	const std::string f = has_nulls ? nptr + "[" + ix_of(src) + "]" : "";
+
+	if (left_src(D, src))
+		return f.empty() ? fmt("h%d", src - 1)
+			: fmt("(h%d && !", src - 1) + f + ")";
+	return f.empty() ? f : "!" + f;
+}
+
+/* Atom q of P.wh as a branch-free boolean over its loaded values va / vb.
+ * Kind, widths and NULL presence are baked, the bounds stay arguments.  A
+ * comparison over a NULL is not true; IS_NULL is true exactly then. */
+static std::string atom_expr(const PlanDev &D, const PlanAtomDev &A, int q,
+			     const std::string &va, const std::string &vb)
+{
+	const std::string P = fmt("P.wh.atoms[%d]", q);
+	const char *a = va.c_str(), *b = vb.c_str(), *p = P.c_str();
+	std::string e;
+
+	if (A.kind >= GG_ATOM_IS_NULL)
+	{
+		e = atom_isnull(D, A.src, A.nulls != nullptr, P + ".nulls");
+		if (A.kind == GG_ATOM_IS_NULL)
+			return e.empty() ? "false" : "(bool) " + e;
+		return e.empty() ? "true" : "!" + e;
+	}
+	switch (A.kind)
+	{
+		case GG_ATOM_RANGE:
+			e = fmt("(%s >= %s.lo) & (%s < %s.hi)", a, p, a, p);
+			break;
+		case GG_ATOM_NOT_RANGE:
+			e = fmt("((%s < %s.lo) | (%s >= %s.hi))", a, p, a, p);
+			break;
+		default:
+			e = fmt("(%s %s %s)", a, A.kind == GG_ATOM_LT ? "<"
+				: A.kind == GG_ATOM_LE ? "<="
+				: A.kind == GG_ATOM_EQ ? "==" : "!=", b);
+	}
+	const std::string na = atom_notnull(D, A.src, A.nulls != nullptr,
+					    P + ".nulls");
+	const std::string nb = A.col2
+		? atom_notnull(D, A.src2, A.nulls2 != nullptr, P + ".nulls2") : "";
+
+	return "(" + e + (na.empty() ? "" : " & " + na) +
+		(nb.empty() ? "" : " & " + nb) + ")";
+}
+
+/* clauses [c0, c1) of P.wh: per clause the loads of its atoms' columns
+ * (value_of names the variable holding a column, emitting the load on first
+ * use), then one test: a clause none of whose atoms is true drops the row */
+template <class ValueOf>
+static void emit_where_clauses(std::string &s, const Gen &G, int c0, int c1,
+			       ValueOf value_of)
+{
+	const PlanWhereDev &W = *G.W;
+	int q = 0;
+
+	for (int c = 0; c < c1; c++)
+	{
+		std::string e;
+
+		for (const int end = q + W.natoms[c]; q < end; q++)
+		{
+			const PlanAtomDev &A = W.atoms[q];
+			std::string va, vb;
+
+			if (c < c0)
+				continue;
+			if (A.kind < GG_ATOM_IS_NULL)
+				va = value_of(A.col, A.width, A.src,
+					      fmt("P.wh.atoms[%d].col", q));
+			if (A.col2)
+				vb = value_of(A.col2, A.width2, A.src2,
+					      fmt("P.wh.atoms[%d].col2", q));
+			e += (e.empty() ? "" : "\n\t\t      | ") +
+				atom_expr(G.D, A, q, va, vb);
+		}
+		if (c >= c0)
+			s += "\t\tif (!(" + e + ")) return false;\n";
+	}
+}
+
 /* ---- per-row evaluation as a macro-free inline sequence ---- */
 static void emit_row_pass(std::string &s, const Gen &G)
 {
@@ -569,6 +715,35 @@ static void emit_row_pass(std::string &s, const Gen &G)
 				 p);
 		s += fmt("\t\tif (v%d < P.preds[%d].lo || v%d >= P.preds[%d].hi) return false;\n",
 			 p, p, p, p);
+	}
+	if (G.W && G.W->nscan)
+	{
+		/* scan clauses, ahead of the joins.  Every atom reads the
+		 * driving row; a column a pred or an earlier atom loaded is
+		 * not loaded again (an IN-list is one load and n compares) */
+		struct Ld
+		{
+			const void *col;
+			int width;
+			std::string var;
+		};
+		std::vector<Ld> have;
+
+		for (int p = 0; p < D.npreds; p++)
+			have.push_back({D.preds[p].col, D.preds[p].width,
+					fmt("v%d", p)});
+		emit_where_clauses(s, G, 0, G.W->nscan,
+				   [&](const void *c, int w, int,
+				       const std::string &ptr) -> std::string
+		{
+			for (auto &h : have)
+				if (h.col == c && h.width == w)
+					return h.var;
+			have.push_back({c, w, fmt("w%d", (int) have.size())});
+			emit_ld(s, have.back().var.c_str(), ptr.c_str(), w, "i",
+				G.nt);
+			return have.back().var;
+		});
 	}
 	for (int j = 0; j < D.njoins; j++)
 		emit_join(s, D, j);
@@ -645,10 +820,25 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 			: fmt("xu%d", u);
 	};
 
+	/* with post-join WHERE clauses the lambda answers "the row survives" */
+	const char *ret = where_post(G) ? " -> bool" : "";
+
 	s += G.payload
 		? fmt("\tauto agg_vals = [&](int64_t i, uint32_t r0, uint32_t r1%s, "
-		      "VAT *av, bool *aok)\n\t{\n", left_flags(D, "bool ").c_str())
-		: "\tauto agg_vals = [&](int64_t i, VAT *av, bool *aok)\n\t{\n";
+		      "VAT *av, bool *aok)%s\n\t{\n",
+		      left_flags(D, "bool ").c_str(), ret)
+		: fmt("\tauto agg_vals = [&](int64_t i, VAT *av, bool *aok)%s\n\t{\n",
+		      ret);
+	/* pass 0: the post-join WHERE clauses, through the load table below,
+	 * so a column that is an atom, a factor and a filter input is loaded
+	 * once; a row they drop leaves before any other load */
+	if (where_post(G))
+		emit_where_clauses(s, G, G.W->nscan, G.W->nclauses,
+				   [&](const void *c, int w, int src,
+				       const std::string &ptr) -> std::string
+		{
+			return fmt("xu%d", var_ld(c, w, src, ptr));
+		});
 	/* pass 1: one load per distinct (pointer, width) */
 	for (int a = 0; a < D.naggs; a++)
 		if (D.aggs[a].kind >= 2)
@@ -763,7 +953,7 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 			s += fmt("\t\tav[%d] = v; }\n", a);
 		}
 	}
-	s += "\t};\n";
+	s += where_post(G) ? "\t\treturn true;\n\t};\n" : "\t};\n";
 }
 
 /* the scan loop's head, shared by every variant: filter, group code
@@ -859,9 +1049,13 @@ static void emit_loop_head(std::string &s, const Gen &G)
 		bool aok[NA];
 
 )GG";
-	s += G.payload ? fmt("\t\tagg_vals(i, r0, r1%s, av, aok);\n",
-			     left_flags(D, "").c_str())
-		       : "\t\tagg_vals(i, av, aok);\n";
+	const std::string call = G.payload
+		? fmt("agg_vals(i, r0, r1%s, av, aok)", left_flags(D, "").c_str())
+		: "agg_vals(i, av, aok)";
+
+	/* a post-join WHERE clause drops the row before it touches a group */
+	s += where_post(G) ? "\t\tif (!" + call + ")\n\t\t\tcontinue;\n"
+		: "\t\t" + call + ";\n";
 }
 
 /* where a row's transition lands */
@@ -1139,7 +1333,7 @@ compile_and_load(const std::string &src, int nbake,
 gg_status
 plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		 std::shared_ptr<void> *out, const long long *bake,
-		 int nbake, bool fast)
+		 int nbake, bool fast, const PlanWhereDev *W)
 {
 	const char *dis = getenv("GG_PLAN_RTC");
 
@@ -1159,7 +1353,7 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	for (int j = 0; j < D.njoins; j++)
 		if (gg_join_builds_map(D.pl.jkind[j]))
 			payload = true;
-	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt, payload};
+	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt, payload, W};
 	std::string s;
 
 	emit_prelude(s, G);
@@ -1193,12 +1387,17 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 }
 
 gg_status
-plan_rtc_launch(hipStream_t s, const std::shared_ptr<void> &h, PlanDev P,
-		int grid, int block)
+plan_rtc_launch(hipStream_t s, const std::shared_ptr<void> &h,
+		const PlanDev &P, int grid, int block, const PlanWhereDev *W)
 {
 	PlanRtc *rtc = (PlanRtc *) h.get();
-	size_t size = plan_arg_bytes(P);
-	void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &P,
+	size_t size = plan_arg_bytes(P, W);
+	PlanDevWhere A;
+
+	A.p = P;
+	if (W)
+		A.wh = *W;
+	void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A,
 			  HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
 			  HIP_LAUNCH_PARAM_END};
 

@@ -94,6 +94,31 @@ class _PlanDesc(ctypes.Structure):
                 ("est_groups", I64)]
 
 
+PLAN_MAX_CLAUSES = 8          # GG_PLAN_MAX_CLAUSES
+PLAN_MAX_ATOMS = 8            # GG_PLAN_MAX_ATOMS
+PLAN_MAX_WHERE_ATOMS = 16     # GG_PLAN_MAX_WHERE_ATOMS
+# gg_plan_atomkind (engine_abi.h)
+ATOM_RANGE, ATOM_NOT_RANGE = 0, 1
+ATOM_LT, ATOM_LE, ATOM_EQ, ATOM_NE = 2, 3, 4, 5
+ATOM_IS_NULL, ATOM_NOT_NULL = 6, 7
+
+
+class _PlanAtom(ctypes.Structure):
+    _fields_ = [("col", ctypes.c_char_p), ("col2", ctypes.c_char_p),
+                ("lo", I64), ("hi", I64), ("kind", ctypes.c_int8),
+                ("src", ctypes.c_int8), ("src2", ctypes.c_int8)]
+
+
+class _PlanClause(ctypes.Structure):
+    _fields_ = [("atoms", _PlanAtom * PLAN_MAX_ATOMS),
+                ("natoms", ctypes.c_int), ("scope", ctypes.c_int8)]
+
+
+class _PlanWhere(ctypes.Structure):
+    _fields_ = [("clauses", _PlanClause * PLAN_MAX_CLAUSES),
+                ("nclauses", ctypes.c_int)]
+
+
 NEG_INF = -(1 << 63)          # one-sided range bounds
 POS_INF = (1 << 63) - 1
 PLAN_NULL_KEY = -(1 << 63) + 1
@@ -267,6 +292,100 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
     return d, kinds
 
 
+def build_plan_where(joins=(), where=()):
+    """The gg_plan_where (engine_abi.h) of a plan's general WHERE clauses:
+    `where` holds the clauses of the plan's WHERE (scope 0), and a join
+    spec's "where" key those of that join's build filter (scope 1+k, over
+    the build table's own columns).  The clauses are ANDed.  Pure: calls
+    neither the library nor a GPU.
+
+    A clause is a list of atoms (ORed), or one atom:
+      ("range", col, lo, hi)       lo <= col < hi
+      ("not_range", col, lo, hi)   col < lo or col >= hi
+      ("eq", col, v) | ("ne", col, v)
+      ("cmp", a, op, b)            two columns, op in < <= = <> > >=
+                                   (> and >= swap the sides)
+      ("is_null", col) | ("not_null", col)
+      ("in", col, [v, ...])        expands to equalities inside its clause
+    and a whole clause ("not_in", col, [v, ...]) expands to one clause per
+    value.  `col` is a name or (join_index, name), as in build_plan_desc.
+    A comparison over a NULL is not true; is_null is true exactly then.
+    More than PLAN_MAX_CLAUSES clauses, PLAN_MAX_ATOMS atoms in a clause or
+    PLAN_MAX_WHERE_ATOMS atoms in all raise ValueError."""
+    ops = {"<": (ATOM_LT, False), "<=": (ATOM_LE, False),
+           "=": (ATOM_EQ, False), "<>": (ATOM_NE, False),
+           ">": (ATOM_LT, True), ">=": (ATOM_LE, True)}
+
+    def colref(c):
+        if isinstance(c, str):
+            return c.encode(), 0
+        k, name = c
+        return name.encode(), 1 + k
+
+    def atoms_of(a):
+        """(kind, (col, src), (col2, src2) | None, lo, hi) per atom"""
+        tag = a[0]
+        if tag == "range":
+            return [(ATOM_RANGE, colref(a[1]), None, int(a[2]), int(a[3]))]
+        if tag == "not_range":
+            return [(ATOM_NOT_RANGE, colref(a[1]), None, int(a[2]),
+                     int(a[3]))]
+        if tag == "eq":
+            return [(ATOM_RANGE, colref(a[1]), None, int(a[2]),
+                     int(a[2]) + 1)]
+        if tag == "ne":
+            return [(ATOM_NOT_RANGE, colref(a[1]), None, int(a[2]),
+                     int(a[2]) + 1)]
+        if tag == "in":
+            return [(ATOM_RANGE, colref(a[1]), None, int(v), int(v) + 1)
+                    for v in a[2]]
+        if tag == "cmp":
+            kind, swap = ops[a[2]]
+            x, y = (a[3], a[1]) if swap else (a[1], a[3])
+            return [(kind, colref(x), colref(y), 0, 0)]
+        if tag == "is_null":
+            return [(ATOM_IS_NULL, colref(a[1]), None, 0, 0)]
+        if tag == "not_null":
+            return [(ATOM_NOT_NULL, colref(a[1]), None, 0, 0)]
+        raise ValueError(f"unknown where atom {a!r}")
+
+    def is_atom(c):
+        return isinstance(c, tuple) and len(c) > 0 and isinstance(c[0], str)
+
+    clauses = []                 # (scope, [atoms])
+    for scope, cl in ([(0, c) for c in where] +
+                      [(1 + j, c) for j, spec in enumerate(joins)
+                       for c in spec.get("where", ())]):
+        if is_atom(cl) and cl[0] == "not_in":
+            for v in cl[2]:
+                clauses.append((scope, atoms_of(("ne", cl[1], v))))
+        elif is_atom(cl):
+            clauses.append((scope, atoms_of(cl)))
+        else:
+            clauses.append((scope, [t for a in cl for t in atoms_of(a)]))
+    if len(clauses) > PLAN_MAX_CLAUSES:
+        raise ValueError(
+            f"a plan holds at most {PLAN_MAX_CLAUSES} where clauses")
+    if sum(len(atoms) for _s, atoms in clauses) > PLAN_MAX_WHERE_ATOMS:
+        raise ValueError(
+            f"a plan holds at most {PLAN_MAX_WHERE_ATOMS} where atoms")
+    w = _PlanWhere()
+    w.nclauses = len(clauses)
+    for c, (scope, atoms) in enumerate(clauses):
+        if len(atoms) > PLAN_MAX_ATOMS:
+            raise ValueError(
+                f"where clause {c}: a clause holds at most "
+                f"{PLAN_MAX_ATOMS} atoms")
+        w.clauses[c].scope = scope
+        w.clauses[c].natoms = len(atoms)
+        for q, (kind, (col, src), b, lo, hi) in enumerate(atoms):
+            t = w.clauses[c].atoms[q]
+            t.kind, t.col, t.src, t.lo, t.hi = kind, col, src, lo, hi
+            if b is not None:
+                t.col2, t.src2 = b
+    return w
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("launches", I64),
                 ("total_ms", ctypes.c_double), ("rows_in", I64),
@@ -329,6 +448,12 @@ def _load():
     lib.gg_engine_comm_init.argtypes = [ctypes.c_void_p]
     lib.gg_engine_compile_plan.argtypes = [ctypes.POINTER(_PlanDesc),
                                            ctypes.POINTER(I32)]
+    lib.gg_engine_compile_plan_where.restype = ctypes.c_int
+    lib.gg_engine_compile_plan_where.argtypes = [
+        ctypes.POINTER(_PlanDesc), ctypes.POINTER(_PlanWhere),
+        ctypes.POINTER(I32)]
+    lib.gg_engine_plan_where_size.argtypes = []
+    lib.gg_engine_plan_where_size.restype = ctypes.c_size_t
     lib.gg_engine_plan_desc_size.argtypes = []
     lib.gg_engine_plan_desc_size.restype = ctypes.c_size_t
     lib.gg_engine_plan_topk_tile.argtypes = []
@@ -605,14 +730,22 @@ class Engine:
 
     # ---- generalized pipeline descriptor (v2) ----
     def compile_plan(self, scan_table, preds=(), joins=(), group_cols=(),
-                     aggs=(), order_by=(), limit=0, est_groups=0):
+                     aggs=(), order_by=(), limit=0, est_groups=0, where=()):
         """Compile a compositional plan (engine_abi.h gg_plan_desc); the
-        arguments are build_plan_desc's."""
+        arguments are build_plan_desc's, and `where` (with the join specs'
+        "where" keys) build_plan_where's.  A plan without a clause goes
+        through gg_engine_compile_plan as ever."""
         d, kinds = build_plan_desc(scan_table, preds, joins, group_cols,
                                    aggs, order_by, limit, est_groups)
+        w = build_plan_where(joins, where)
         h = I32()
-        _check(lib().gg_engine_compile_plan(ctypes.byref(d),
-                                            ctypes.byref(h)), "compile_plan")
+        if w.nclauses:
+            _check(lib().gg_engine_compile_plan_where(
+                ctypes.byref(d), ctypes.byref(w), ctypes.byref(h)),
+                "compile_plan")
+        else:
+            _check(lib().gg_engine_compile_plan(
+                ctypes.byref(d), ctypes.byref(h)), "compile_plan")
         self._plan_kinds[h.value] = kinds
         if d.limit > 0:
             self._plan_limit[h.value] = d.limit

@@ -815,6 +815,135 @@ gg_status gg_engine_compile_plan(const gg_plan_desc *desc, gg_pipeline *out);
  * its mirror of the layout without a GPU */
 size_t gg_engine_plan_desc_size(void);
 
+/* General WHERE clauses: a normalised boolean qual handed over BESIDE the
+ * descriptor (gg_plan_desc keeps its layout; bindings pin its last field).
+ * The preds of a scan, a build side or a filter are conjunctions of ranges
+ * over one table's own columns; this extension adds OR, IN-lists, negated
+ * ranges, column-against-column comparisons (also across a join, against a
+ * payload column) and IS [NOT] NULL, for the plan's WHERE and for the build
+ * filter of each join.
+ *
+ * Form.  Conjunctive normal form with negation only at the atoms:
+ *   qual   = clauses[0] AND clauses[1] AND ...      (ExecEvalAnd)
+ *   clause = atoms[0] OR atoms[1] OR ...            (ExecEvalOr)
+ *   atom   = one of gg_plan_atomkind; ExecEvalNot never appears above an
+ *            atom, the shim pushes it down: NOT (lo <= a < hi) is
+ *            NOT_RANGE, NOT (a < b) is b <= a, NOT (a = b) is NE,
+ *            NOT (a IS NULL) is NOT_NULL (ExecEvalNullTest in execQual.c).
+ *   IN-list (ExecEvalScalarArrayOp, useOr): one clause of equalities
+ *            [v, v+1); NOT IN (v1..vn) of constants (useOr false): n
+ *            one-atom clauses of NOT_RANGE [v, v+1).
+ * The shim normalises the plan's qual into this form and falls back when
+ * it does not fit the limits.
+ *
+ * An atom is either true or not true.
+ *   RANGE, NOT_RANGE, LT, LE, EQ, NE: not true when any column the atom
+ *     reads is SQL NULL (the NULL-flag rule of the preds), else the literal
+ *     comparison.
+ *   IS_NULL: true exactly when a is SQL NULL; NOT_NULL is its complement.
+ *   A column with no NULL-flag array is never NULL by itself; every column
+ *     of source 1+k is NULL on a row LEFT join k NULL-extended.
+ * A clause is true iff some atom is true; the qual is true iff every
+ * clause is true; a row whose qual is not true is dropped (ExecQual: a
+ * qual result of false or NULL rejects the tuple).
+ *
+ * Why two values are exact.  SQL's logic is three-valued (Kleene).  Read
+ * "not true" as {FALSE, NULL}.  Negation sits only inside the atoms, and a
+ * negated comparison over a NULL is still NULL, so each atom's "true" is
+ * exactly Kleene TRUE.  OR is TRUE iff some operand is TRUE, AND is TRUE iff
+ * every operand is TRUE: both depend only on which operands are TRUE, never
+ * on whether a non-true operand is FALSE or NULL.  With no negation above
+ * the atoms, "TRUE under Kleene logic" and "some atom true in every clause"
+ * therefore coincide, and ExecQual keeps exactly the TRUE rows.
+ *
+ * Scope 0 is the plan's WHERE.  A driving row survives iff its scan.preds
+ * pass, every join keeps it and every scope-0 clause is true.  Atoms follow
+ * the "column sources" rule: src / src2 = 0 is the driving table, 1+k the
+ * build table of INNER or LEFT join k, read at the joined build row.  On a
+ * row LEFT join k NULL-extended every column of source 1+k is NULL:
+ * comparisons over it are not true, IS_NULL is true.  Unlike an aggregate
+ * filter, a WHERE clause decides which rows and so which groups exist; with
+ * ngroup == 0 and no surviving row the plan still yields its one row.  The
+ * WHERE is evaluated per segment, ahead of the cross-segment combine.
+ *
+ * Scope 1+k is an additional build filter of join k: a build row can be a
+ * partner iff it passes joins[k].build.preds AND every scope-1+k clause.
+ * Its atoms name columns of that build table; src and src2 must be 0.  For
+ * a LEFT join these are ON-clause conditions on the nullable side and never
+ * drop a driving row.  Uniqueness and duplicate detection count only rows
+ * passing both, as for the preds.  All four join kinds take them.
+ *
+ * Comparisons.  LT, LE, EQ, NE compare the two values widened to int64 as
+ * the plan reads them everywhere (char1 is 0..255, int32 sign-extended) with
+ * a true comparison, never a subtraction: INT64_MIN < INT64_MAX holds.  > and
+ * >= are LT / LE with the sides swapped.  A comparison in which exactly one
+ * side is GG_COL_DEC64_S2 is GG_ENOTSUP (the scales differ).
+ *
+ * Ranges.  RANGE and NOT_RANGE are literal: NOT_RANGE is the exact complement
+ * of RANGE on non-NULL values whatever lo / hi are, INT64_MIN / INT64_MAX
+ * included.  Equality is [v, v+1), <> v its NOT_RANGE.
+ *
+ * where == NULL or nclauses == 0 is gg_engine_compile_plan exactly: same
+ * validation, same kernels, same generated program text.  Everything else in
+ * the descriptor composes unchanged (aggregate filters, ORDER BY / LIMIT,
+ * est_groups growth, packed group pairs, n_segments > 1); packed ranges are
+ * taken over whole columns and do not depend on the WHERE.
+ *
+ * Stat rows: path_plan_where counts one per execute of a plan with at least
+ * one clause; hbm_bytes_algorithmic counts each distinct (column, source) of
+ * the scope-0 clauses once, at its width (an 8-value IN-list reads its
+ * column once).
+ *
+ * Errors.  GG_ENOTSUP: nclauses outside [0, GG_PLAN_MAX_CLAUSES], natoms >
+ * GG_PLAN_MAX_ATOMS, more than GG_PLAN_MAX_WHERE_ATOMS atoms in all, an
+ * unknown atom kind, a mixed-scale comparison.  GG_EINVAL: natoms <= 0 (an
+ * empty disjunction), scope outside [0, njoins], a missing column, a col2 on
+ * a non-comparison atom or none on a comparison, a source naming a SEMI or
+ * ANTI join or a join >= njoins, or anything but 0 in a build scope. */
+#define GG_PLAN_MAX_CLAUSES      8	/* per gg_plan_where */
+#define GG_PLAN_MAX_ATOMS        8	/* per clause */
+#define GG_PLAN_MAX_WHERE_ATOMS 16	/* per gg_plan_where, all clauses */
+
+typedef enum gg_plan_atomkind
+{
+	GG_ATOM_RANGE = 0,	/* lo <= a < hi (what gg_plan_pred says) */
+	GG_ATOM_NOT_RANGE = 1,	/* a < lo || a >= hi: <>, NOT BETWEEN */
+	GG_ATOM_LT = 2,		/* a <  b   (b = col2; > and >= by swapping) */
+	GG_ATOM_LE = 3,		/* a <= b */
+	GG_ATOM_EQ = 4,		/* a =  b */
+	GG_ATOM_NE = 5,		/* a <> b */
+	GG_ATOM_IS_NULL = 6,	/* a IS NULL */
+	GG_ATOM_NOT_NULL = 7	/* a IS NOT NULL */
+} gg_plan_atomkind;
+
+typedef struct gg_plan_atom
+{
+	const char *col;	/* a */
+	const char *col2;	/* b for LT/LE/EQ/NE, else must be NULL */
+	int64_t lo, hi;		/* RANGE / NOT_RANGE */
+	int8_t kind, src, src2;	/* gg_plan_atomkind; column sources of a, b */
+} gg_plan_atom;
+
+typedef struct gg_plan_clause		/* atoms[0] OR atoms[1] OR ... */
+{
+	gg_plan_atom atoms[GG_PLAN_MAX_ATOMS];
+	int natoms;
+	int8_t scope;	/* 0 = the plan's WHERE; 1+k = build filter of join k */
+} gg_plan_clause;
+
+typedef struct gg_plan_where		/* clauses[0] AND clauses[1] ... */
+{
+	gg_plan_clause clauses[GG_PLAN_MAX_CLAUSES];
+	int nclauses;
+} gg_plan_where;
+
+gg_status gg_engine_compile_plan_where(const gg_plan_desc *desc,
+				       const gg_plan_where *where,
+				       gg_pipeline *out);
+
+/* sizeof(gg_plan_where), for bindings; needs no GPU */
+size_t gg_engine_plan_where_size(void);
+
 /* Rows per tile of the device top-k's tournament (a power of two, at least
  * 2 * GG_PLAN_MAX_LIMIT): group counts around it are where the selection
  * takes another round.  A constant of the build; needs no GPU. */
