@@ -4000,6 +4000,8 @@ gg_engine_text_dict_encode(const uint8_t *pool, const uint64_t *offs,
 			st = fail(GG_EINVAL, "dictionary overflow "
 				  "(%zu > %d)", ents.size(),
 				  (int) max_dict);
+		std::vector<int32_t> slot_to_id;
+
 		if (st == GG_OK)
 		{
 			std::sort(ents.begin(), ents.end(),
@@ -4016,8 +4018,9 @@ gg_engine_text_dict_encode(const uint8_t *pool, const uint64_t *offs,
 				  return sa[z] < sb[z];
 				  return la < lb;
 				  });
-			std::vector<int32_t> slot_to_id(nslots, -1);
 			int64_t dpos = 0;
+
+			slot_to_id.assign(nslots, -1);
 
 			dict_offs[0] = 0;
 			for (size_t id = 0; id < ents.size(); id++)
@@ -4026,17 +4029,31 @@ gg_engine_text_dict_encode(const uint8_t *pool, const uint64_t *offs,
 				uint32_t l = lens[ents[id].row];
 
 				if (dpos + l > dict_cap)
-					return fail(GG_EINVAL,
-						    "dict_cap too small");
+				{
+					/* through the free block below */
+					st = fail(GG_EINVAL,
+						  "dict_cap too small");
+					break;
+				}
 				std::memcpy(dict_bytes + dpos,
 					    pool + offs[ents[id].row], l);
 				dpos += l;
 				dict_offs[id + 1] = dpos;
 			}
+		}
+		if (st == GG_OK)
+		{
 			*out_ndict = (int32_t) ents.size();
-			GG_HIP(hipMemcpy(d_map, slot_to_id.data(),
-					 nslots * 4,
-					 hipMemcpyHostToDevice));
+			{
+				hipError_t he = hipMemcpy(
+					d_map, slot_to_id.data(), nslots * 4,
+					hipMemcpyHostToDevice);
+
+				if (he != hipSuccess)
+					st = fail(GG_EGPU, "td_map upload: %s",
+						  hipGetErrorString(he));
+			}
+			if (st == GG_OK)
 			{
 				hipError_t he = launch_td_map(
 					e.stream, d_rowslot, n, d_map,
@@ -4912,24 +4929,28 @@ gg_engine_hash_join_i64_spill(const int64_t *build_keys,
 		int64_t b_n = (int64_t) bk[p2].size();
 		int64_t p_n = (int64_t) pk[p2].size();
 
-		if (b_n == 0 || p_n == 0)
+		/* a partition without probe rows still builds: the build is
+		 * what checks its keys (0, duplicates) */
+		if (b_n == 0)
 			continue;
+		const size_t p_sz = (size_t) (p_n ? p_n : 1) * 8;
 		uint64_t nslots = next_pow2(2 * (uint64_t) b_n);
 		/* engine pools: no per-partition hipMalloc/free; pinned
 		 * bounce for the uploads (pageable hipMemcpy was the
 		 * serial cost here, like the group-by reload) */
 		int64_t *d_bk = (int64_t *) e.esget("sj.bk", (size_t) b_n * 8);
 		int64_t *d_bv = (int64_t *) e.esget("sj.bv", (size_t) b_n * 8);
-		int64_t *d_pk = (int64_t *) e.esget("sj.pk", (size_t) p_n * 8);
-		int64_t *d_pi = (int64_t *) e.esget("sj.pi", (size_t) p_n * 8);
-		int64_t *d_oi = (int64_t *) e.esget("sj.oi", (size_t) p_n * 8);
-		int64_t *d_ov = (int64_t *) e.esget("sj.ov", (size_t) p_n * 8);
+		int64_t *d_pk = (int64_t *) e.esget("sj.pk", p_sz);
+		int64_t *d_pi = (int64_t *) e.esget("sj.pi", p_sz);
+		int64_t *d_oi = (int64_t *) e.esget("sj.oi", p_sz);
+		int64_t *d_ov = (int64_t *) e.esget("sj.ov", p_sz);
 		unsigned long long *tk = (unsigned long long *)
 			e.esget("sj.tk", nslots * 8);
 		unsigned long long *tv = (unsigned long long *)
 			e.esget("sj.tv", nslots * 8);
+		/* ctr[0] = match count, ctr[1] = k_sj_build's error word */
 		unsigned long long *ctr = (unsigned long long *)
-			e.esget("sj.ctr", 8);
+			e.esget("sj.ctr", 16);
 		int64_t *hb = (int64_t *)
 			e.ehget("sj.hb", (size_t) (b_n > p_n ? b_n : p_n) * 8);
 
@@ -4943,7 +4964,7 @@ gg_engine_hash_join_i64_spill(const int64_t *build_keys,
 				  hipGetErrorString(e_)); }
 		auto up = [&](int64_t *dst, const int64_t *src, int64_t nn)
 		{
-			if (st != GG_OK)
+			if (st != GG_OK || nn == 0)
 				return;
 			int64_t nblk = (nn + (1 << 17) - 1) >> 17;
 
@@ -4968,21 +4989,31 @@ gg_engine_hash_join_i64_spill(const int64_t *build_keys,
 			up(d_pi, pi[p2].data(), p_n);
 			GG_HIP_BRK(hipMemsetAsync(tk, 0, nslots * 8,
 						  e.stream));
-			GG_HIP_BRK(hipMemsetAsync(ctr, 0, 8, e.stream));
+			GG_HIP_BRK(hipMemsetAsync(ctr, 0, 16, e.stream));
 			GG_HIP_BRK(launch_sj_build(e.stream, d_bk, d_bv,
-						   b_n, tk, tv, nslots));
-			GG_HIP_BRK(launch_sj_probe(e.stream, d_pk, d_pi,
-						   p_n, tk, tv, nslots,
-						   d_oi, d_ov, ctr));
+						   b_n, tk, tv, nslots,
+						   ctr + 1));
+			if (p_n)
+				GG_HIP_BRK(launch_sj_probe(e.stream, d_pk, d_pi,
+							   p_n, tk, tv, nslots,
+							   d_oi, d_ov, ctr));
 			GG_HIP_BRK(hipStreamSynchronize(e.stream));
 		}
 
-		unsigned long long nm = 0;
+		unsigned long long hctr[2] = {0, 0};
 
 		if (st == GG_OK)
-			GG_HIP_BRK(hipMemcpy(&nm, ctr, 8,
+			GG_HIP_BRK(hipMemcpy(hctr, ctr, 16,
 					     hipMemcpyDeviceToHost));
-		if (st == GG_OK && total + (int64_t) nm > cap)
+		const unsigned long long nm = hctr[0];
+
+		if (st == GG_OK && (hctr[1] & SJ_ERR_ZERO_KEY))
+			st = fail(GG_EINVAL, "join build key 0 is reserved "
+				  "(the table's empty sentinel)");
+		else if (st == GG_OK && (hctr[1] & SJ_ERR_DUP_KEY))
+			st = fail(GG_EINVAL, "join build keys must be unique: "
+				  "duplicate build key");
+		else if (st == GG_OK && total + (int64_t) nm > cap)
 			st = fail(GG_EINVAL, "join cap %lld < %lld",
 				  (long long) cap,
 				  (long long) (total + (int64_t) nm));
@@ -5035,6 +5066,7 @@ gg_engine_hash_groupby_i64_spill(const int64_t *keys, const int64_t *vals,
 	    !out_counts || !out_ngroups || !out_npartitions ||
 	    budget_bytes < (1 << 20))
 		return fail(GG_EINVAL, "bad groupby_spill args");
+	*out_ngroups = 0;
 
 	/* in-memory fast path: input pairs + 2x table + compact buffers
 	 * ≈ 7 x n x 8 bytes */
@@ -5111,6 +5143,7 @@ gg_engine_hash_groupby_i64_spill(const int64_t *keys, const int64_t *vals,
 			int64_t *hk = nullptr, *hv = nullptr;	/* pinned in */
 			int64_t *pok = nullptr, *pos = nullptr,
 				*poc = nullptr;			/* pinned out */
+			/* [0] group count, [1] INT64_MIN-key flag */
 			unsigned long long *dctr = nullptr;
 			unsigned long long *hng = nullptr;	/* pinned */
 			hipStream_t stm = nullptr;
@@ -5136,13 +5169,13 @@ gg_engine_hash_groupby_i64_spill(const int64_t *keys, const int64_t *vals,
 			aok =
 				RL_POOL(dk, esget, (size_t) maxm * 8) &&
 				RL_POOL(dv, esget, (size_t) maxm * 8) &&
-				RL_POOL(dctr, esget, 8) &&
+				RL_POOL(dctr, esget, 16) &&
 				RL_POOL(hk, ehget, (size_t) maxm * 8) &&
 				RL_POOL(hv, ehget, (size_t) maxm * 8) &&
 				RL_POOL(pok, ehget, (size_t) maxm * 8) &&
 				RL_POOL(pos, ehget, (size_t) maxm * 8) &&
 				RL_POOL(poc, ehget, (size_t) maxm * 8) &&
-				RL_POOL(hng, ehget, 8) &&
+				RL_POOL(hng, ehget, 16) &&
 				hipStreamCreate(&q.stm) == hipSuccess &&
 				hipEventCreate(&q.done) == hipSuccess;
 #undef RL_POOL
@@ -5164,8 +5197,15 @@ gg_engine_hash_groupby_i64_spill(const int64_t *keys, const int64_t *vals,
 			q.busy = false;
 			if (st != GG_OK)
 				return;
-			int64_t ng = (int64_t) *q.hng;
+			int64_t ng = (int64_t) q.hng[0];
 
+			if (q.hng[1])
+			{
+				st = fail(GG_EINVAL,
+					  "group key INT64_MIN is reserved "
+					  "(the table's empty sentinel)");
+				return;
+			}
 			if (ng_total + ng > cap)
 			{
 				st = fail(GG_EINVAL,
@@ -5243,15 +5283,15 @@ gg_engine_hash_groupby_i64_spill(const int64_t *keys, const int64_t *vals,
 						  q.stm));
 			GG_HIP_GBR(hipMemsetAsync(tc, 0, rslots * 8,
 						  q.stm));
-			GG_HIP_GBR(hipMemsetAsync(q.dctr, 0, 8, q.stm));
+			GG_HIP_GBR(hipMemsetAsync(q.dctr, 0, 16, q.stm));
 			GG_HIP_GBR(launch_groupby_build(q.stm, q.dk, q.dv,
 							m, tk, ts, tc,
-							rslots));
+							rslots, q.dctr + 1));
 			GG_HIP_GBR(launch_groupby_compact(
 				q.stm, tk, ts, tc, rslots, q.pok, q.pos,
 				q.poc, q.dctr, (uint64_t) maxm));
 			GG_HIP_GBR(hipEventRecord(tbl_free, q.stm));
-			GG_HIP_GBR(hipMemcpyAsync(q.hng, q.dctr, 8,
+			GG_HIP_GBR(hipMemcpyAsync(q.hng, q.dctr, 16,
 						  hipMemcpyDeviceToHost,
 						  q.stm));
 			GG_HIP_GBR(hipEventRecord(q.done, q.stm));
@@ -5361,8 +5401,9 @@ gg_engine_hash_groupby_i64(const int64_t *keys, const int64_t *vals,
 	int64_t *ok = (int64_t *) e.esget("gb.ok", (size_t) n * 8);
 	int64_t *os = (int64_t *) e.esget("gb.os", (size_t) n * 8);
 	int64_t *oc = (int64_t *) e.esget("gb.oc", (size_t) n * 8);
+	/* ctr[0] = group count, ctr[1] = the build's INT64_MIN-key flag */
 	unsigned long long *ctr = (unsigned long long *)
-		e.esget("gb.ctr", 8);
+		e.esget("gb.ctr", 16);
 
 	if (!dk || !dv || !tk || !ts || !tc || !ok || !os || !oc || !ctr)
 		return fail(GG_ENOMEM, "groupby buffers");
@@ -5371,7 +5412,7 @@ gg_engine_hash_groupby_i64(const int64_t *keys, const int64_t *vals,
 	GG_HIP(launch_fill_u64(e.stream, tk, nslots, 0x8000000000000000ull));
 	GG_HIP(hipMemsetAsync(ts, 0, nslots * 8, e.stream));
 	GG_HIP(hipMemsetAsync(tc, 0, nslots * 8, e.stream));
-	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
+	GG_HIP(hipMemsetAsync(ctr, 0, 16, e.stream));
 	/* chunked pinned upload overlapped with the build: the build
 	 * kernel is per-row independent (CAS find-or-create + atomic
 	 * transitions), so it runs on each chunk as it lands — a
@@ -5445,7 +5486,8 @@ gg_engine_hash_groupby_i64(const int64_t *keys, const int64_t *vals,
 							  up[it], 0);
 				if (launch_groupby_build(
 					e.stream, dk + base, dv + base, m,
-					tk, ts, tc, nslots) != hipSuccess)
+					tk, ts, tc, nslots, ctr + 1)
+				    != hipSuccess)
 				{
 					st2 = fail(GG_EGPU,
 						   "groupby build");
@@ -5468,7 +5510,8 @@ gg_engine_hash_groupby_i64(const int64_t *keys, const int64_t *vals,
 			if (e1 != hipSuccess || e2 != hipSuccess)
 				st2 = fail(GG_EGPU, "groupby H2D");
 			else if (launch_groupby_build(e.stream, dk, dv, n,
-						      tk, ts, tc, nslots)
+						      tk, ts, tc, nslots,
+						      ctr + 1)
 				 != hipSuccess)
 				st2 = fail(GG_EGPU, "groupby build");
 		}
@@ -5479,12 +5522,16 @@ gg_engine_hash_groupby_i64(const int64_t *keys, const int64_t *vals,
 				      oc, ctr, (uint64_t) n));
 	GG_HIP(hipStreamSynchronize(e.stream));
 
-	unsigned long long ng = 0;
+	unsigned long long hctr[2] = {0, 0};
 
-	GG_HIP(hipMemcpy(&ng, ctr, 8, hipMemcpyDeviceToHost));
+	GG_HIP(hipMemcpy(hctr, ctr, 16, hipMemcpyDeviceToHost));
+	const unsigned long long ng = hctr[0];
 	gg_status st = GG_OK;
 
-	if ((int64_t) ng > cap)
+	if (hctr[1])
+		st = fail(GG_EINVAL, "group key INT64_MIN is reserved "
+			  "(the table's empty sentinel)");
+	else if ((int64_t) ng > cap)
 		st = fail(GG_EINVAL, "groupby cap %lld < %llu groups",
 			  (long long) cap, ng);
 	if (st == GG_OK && ng)

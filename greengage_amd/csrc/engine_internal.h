@@ -532,10 +532,14 @@ hipError_t launch_fill_u64(hipStream_t s, unsigned long long *p,
 			   uint64_t n, unsigned long long v);
 hipError_t launch_narrow_i32_u8(hipStream_t s, const int32_t *in,
 				int64_t n, uint8_t *out);
+/* bits k_sj_build raises in its error word */
+#define SJ_ERR_ZERO_KEY 1ull	/* build key 0: the table's empty sentinel */
+#define SJ_ERR_DUP_KEY 2ull	/* build key not unique */
 hipError_t launch_sj_build(hipStream_t s, const int64_t *keys,
 			   const int64_t *vals, int64_t n,
 			   unsigned long long *tkeys,
-			   unsigned long long *tvals, uint64_t nslots);
+			   unsigned long long *tvals, uint64_t nslots,
+			   unsigned long long *err);
 hipError_t launch_sj_probe(hipStream_t s, const int64_t *keys,
 			   const int64_t *idxs, int64_t n,
 			   const unsigned long long *tkeys,
@@ -557,11 +561,14 @@ hipError_t launch_gb_part_scatter(hipStream_t s, const int64_t *keys,
 				  const int64_t *vals, int64_t n, int shift,
 				  unsigned long long *cursors,
 				  int64_t *out_k, int64_t *out_v);
+/* *err is set nonzero when a key equals the empty sentinel (INT64_MIN);
+ * such a row is left out of the table */
 hipError_t launch_groupby_build(hipStream_t s, const int64_t *keys,
 				const int64_t *vals, int64_t n,
 				unsigned long long *tkeys,
 				unsigned long long *tsum,
-				unsigned long long *tcnt, uint64_t nslots);
+				unsigned long long *tcnt, uint64_t nslots,
+				unsigned long long *err);
 hipError_t launch_groupby_compact(hipStream_t s,
 				  const unsigned long long *tkeys,
 				  const unsigned long long *tsum,

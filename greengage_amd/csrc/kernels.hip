@@ -2288,12 +2288,18 @@ launch_narrow_i32_u8(hipStream_t s, const int32_t *in, int64_t n,
 /* generic i64-key hash-join kernels for the spill tier
  * (ExecHashJoin batching semantics, nodeHash.c:713): CAS-insert build
  * (key 0 reserved as empty, like the pipeline tables), probe emits
- * (probe_row_index, build_val) matches via wave-aggregated append */
+ * (probe_row_index, build_val) matches via wave-aggregated append.
+ * The build refuses what the table cannot represent: a key 0 (it would
+ * "match" the first empty slot without occupying it) raises
+ * SJ_ERR_ZERO_KEY in *err, a key already in the table (the CAS hands the
+ * key itself back to exactly one of the two rows) SJ_ERR_DUP_KEY; the
+ * host turns either into GG_EINVAL.  A probe key 0 matches nothing. */
 __global__ void
 k_sj_build(const int64_t *__restrict__ keys,
 	   const int64_t *__restrict__ vals, int64_t n,
 	   unsigned long long *__restrict__ tkeys,
-	   unsigned long long *__restrict__ tvals, uint64_t nslots)
+	   unsigned long long *__restrict__ tvals, uint64_t nslots,
+	   unsigned long long *__restrict__ err)
 {
 	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
 
@@ -2303,15 +2309,25 @@ k_sj_build(const int64_t *__restrict__ keys,
 		int64_t kk = keys[i];
 		uint64_t pos = (uint64_t) gg_hashint8(kk) & (nslots - 1);
 
+		if (kk == 0)
+		{
+			atomicOr(err, SJ_ERR_ZERO_KEY);
+			continue;
+		}
 		for (;;)
 		{
 			unsigned long long prev =
 				atomicCAS(&tkeys[pos], 0ull,
 					  (unsigned long long) kk);
 
-			if (prev == 0 || prev == (unsigned long long) kk)
+			if (prev == 0)
 			{
 				tvals[pos] = (unsigned long long) vals[i];
+				break;
+			}
+			if (prev == (unsigned long long) kk)
+			{
+				atomicOr(err, SJ_ERR_DUP_KEY);
 				break;
 			}
 			pos = (pos + 1) & (nslots - 1);
@@ -2338,6 +2354,8 @@ k_sj_probe(const int64_t *__restrict__ keys,
 		int64_t kk = keys[i];
 		uint64_t pos = (uint64_t) gg_hashint8(kk) & (nslots - 1);
 
+		if (kk == 0)	/* would equal the first empty slot */
+			return false;
 		for (;;)
 		{
 			unsigned long long cur = tkeys[pos];
@@ -2392,10 +2410,11 @@ k_sj_probe(const int64_t *__restrict__ keys,
 hipError_t
 launch_sj_build(hipStream_t s, const int64_t *keys, const int64_t *vals,
 		int64_t n, unsigned long long *tkeys,
-		unsigned long long *tvals, uint64_t nslots)
+		unsigned long long *tvals, uint64_t nslots,
+		unsigned long long *err)
 {
 	hipLaunchKernelGGL(k_sj_build, dim3(grid_for(n)), dim3(THREADS), 0,
-			   s, keys, vals, n, tkeys, tvals, nslots);
+			   s, keys, vals, n, tkeys, tvals, nslots, err);
 	return hipGetLastError();
 }
 
@@ -2636,7 +2655,8 @@ k_groupby_build(const int64_t *__restrict__ keys,
 		const int64_t *__restrict__ vals, int64_t n,
 		unsigned long long *__restrict__ tkeys,
 		unsigned long long *__restrict__ tsum,
-		unsigned long long *__restrict__ tcnt, uint64_t nslots)
+		unsigned long long *__restrict__ tcnt, uint64_t nslots,
+		unsigned long long *__restrict__ err)
 {
 	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
 
@@ -2647,6 +2667,14 @@ k_groupby_build(const int64_t *__restrict__ keys,
 		int64_t v = nt_ld64(&vals[i]);
 		uint64_t pos = (uint64_t) gg_hashint8(k) & (nslots - 1);
 
+		/* the empty sentinel as a key would add into the first empty
+		 * slot without claiming it: refuse the row, the host reports
+		 * GG_EINVAL */
+		if ((unsigned long long) k == GB_EMPTY)
+		{
+			atomicOr(err, 1ull);
+			continue;
+		}
 		for (;;)
 		{
 			unsigned long long cur = tkeys[pos];
@@ -2699,10 +2727,10 @@ hipError_t
 launch_groupby_build(hipStream_t s, const int64_t *keys, const int64_t *vals,
 		     int64_t n, unsigned long long *tkeys,
 		     unsigned long long *tsum, unsigned long long *tcnt,
-		     uint64_t nslots)
+		     uint64_t nslots, unsigned long long *err)
 {
 	hipLaunchKernelGGL(k_groupby_build, dim3(grid_for(n)), dim3(THREADS),
-			   0, s, keys, vals, n, tkeys, tsum, tcnt, nslots);
+			   0, s, keys, vals, n, tkeys, tsum, tcnt, nslots, err);
 	return hipGetLastError();
 }
 

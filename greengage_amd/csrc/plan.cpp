@@ -1746,15 +1746,22 @@ gg_engine_hash_groupby_i64_n(const int64_t *keys, const uint8_t *key_nulls,
 	if (!keys || !vals || n < 0 || !out_keys || !out_sums ||
 	    !out_counts || !out_ngroups)
 		return fail(GG_EINVAL, "bad groupby_n args");
+	*out_ngroups = 0;
 	std::vector<int64_t> k2((size_t) n), v2((size_t) n);
 
 	for (int64_t i = 0; i < n; i++)
 	{
+		const bool knull = key_nulls && key_nulls[i];
+
 		if (keys[i] == INT64_MIN)
 			return fail(GG_EINVAL,
 				    "group key INT64_MIN unsupported");
-		k2[i] = (key_nulls && key_nulls[i]) ? GG_PLAN_NULL_KEY
-			: keys[i];
+		/* the NULL group's code: a real key of that value would
+		 * merge into the NULL group */
+		if (!knull && keys[i] == GG_PLAN_NULL_KEY)
+			return fail(GG_EINVAL, "group key INT64_MIN+1 "
+				    "(GG_PLAN_NULL_KEY) unsupported");
+		k2[i] = knull ? GG_PLAN_NULL_KEY : keys[i];
 		v2[i] = (val_nulls && val_nulls[i]) ? 0 : vals[i];
 	}
 	GG_TRY(gg_engine_hash_groupby_i64(k2.data(), v2.data(), n, out_keys,

@@ -373,8 +373,11 @@ gg_status gg_engine_aocs_decode_ao(const uint8_t *stream,
 
 /* General hash group-by (execHHashagg.c find-or-create semantics on
  * arbitrary int64 keys, SUM+COUNT transitions): host buffers in,
- * groups out sorted by key ascending.  Keys may be any int64 except
- * INT64_MIN (the open-addressing empty sentinel).  Returns the group
+ * groups out sorted by key ascending.  Sums wrap as two's-complement
+ * int64.  Keys may be any int64 except INT64_MIN (the open-addressing
+ * empty sentinel): a key of INT64_MIN anywhere in the input returns
+ * GG_EINVAL with *out_ngroups = 0 (detected on the device while the
+ * table is built; the message names INT64_MIN).  Returns the group
  * count; fails with GG_EINVAL if cap is too small. */
 gg_status gg_engine_hash_groupby_i64(const int64_t *keys,
 				     const int64_t *vals, int64_t n,
@@ -387,12 +390,20 @@ gg_status gg_engine_hash_groupby_i64(const int64_t *keys,
  * memory, and aggregated partition by partition (the reference's
  * spill_hash_table/agg_hash_reload semantics,
  * execHHashagg.c:1350/:1852).  Results identical to the in-memory
- * path; out_npartitions reports the fan-out (1 = no spill). */
+ * path, the GG_EINVAL for a key of INT64_MIN included;
+ * out_npartitions reports the fan-out (1 = no spill).  budget_bytes
+ * below 1 MiB, or an input that needs more than 4096 partitions under
+ * it, is GG_EINVAL.  (Declared below, after the join.) */
 /* Spill-tier hash JOIN (nodeHash.c:713 batching): both sides hash-
  * range partitioned on the GPU, staged in host memory, each partition
- * pair built+probed on the GPU.  Build keys must be unique (PK-side
- * build).  Key 0 is reserved (table empty sentinel), as in the
- * pipeline joins.  Output: (probe_row_index, build_val) per match. */
+ * pair built+probed on the GPU.  Output: (probe_row_index, build_val)
+ * per match, in no particular order.
+ * Build keys must be unique (PK-side build): a duplicate build key
+ * returns GG_EINVAL, detected on the device while the table is built.
+ * Key 0 is reserved (table empty sentinel), as in the pipeline joins:
+ * a build key 0 returns GG_EINVAL, and a probe key 0 matches nothing.
+ * Either error leaves *out_nmatch = 0.  budget_bytes below 1 MiB, or
+ * more than 4096 partitions under it, is GG_EINVAL. */
 gg_status gg_engine_hash_join_i64_spill(const int64_t *build_keys,
 					const int64_t *build_vals,
 					int64_t nb,
@@ -970,7 +981,9 @@ gg_status gg_engine_table_set_nulls(gg_table t, const char *col,
  * nodeAgg.c:413 strict transitions): NULL keys form one group
  * (reported as GG_PLAN_NULL_KEY); NULL vals are skipped by both SUM
  * and COUNT (the strict SUM/AVG transition pair).  key_nulls/
- * val_nulls may be NULL (= no NULLs).  Keys INT64_MIN rejected. */
+ * val_nulls may be NULL (= no NULLs).  A key of INT64_MIN (NULL-flagged
+ * or not), or a non-NULL key equal to GG_PLAN_NULL_KEY (it would merge
+ * into the NULL group), returns GG_EINVAL with *out_ngroups = 0. */
 gg_status gg_engine_hash_groupby_i64_n(const int64_t *keys,
 				       const uint8_t *key_nulls,
 				       const int64_t *vals,
