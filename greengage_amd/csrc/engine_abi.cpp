@@ -1294,9 +1294,19 @@ static bool q1_pack_enabled()
 	return !(s && s[0] == '0');
 }
 
+/* GG_Q1_PACK=12 keeps a compile from choosing the 8 B tier (the A/B leg);
+ * read when the companion is built, an existing one is used as it is */
+static bool q1_pack8_allowed()
+{
+	const char *s = getenv("GG_Q1_PACK");
+
+	return !(s && strcmp(s, "12") == 0);
+}
+
 /*
  * Plan-time build of the table's packed Q1 companion (q1_pack.h), once per
- * table.  A table that lacks a Q1 column or is not eligible is remembered
+ * table, in the narrowest tier it fits: only that tier's arrays are
+ * allocated.  A table that lacks a Q1 column or is not eligible is remembered
  * as such; a failed allocation leaves the decision open, clears the HIP
  * error and lets Q1 run the wide kernel, so a table that only just fits in
  * HBM keeps working.  The build's time goes to pipeline p's stats.
@@ -1345,8 +1355,11 @@ static gg_status q1_pack_prepare(Engine &e, Table *t, Pipeline *p)
 		k.state = -1;
 		return GG_OK;
 	}
+	const bool t8 = q1_pack8_allowed() && q1_pack8_eligible(t->nrows, r);
+
 	if (hipMalloc((void **) &k.w8, (size_t) t->nrows * 8) != hipSuccess ||
-	    hipMalloc((void **) &k.w4, (size_t) t->nrows * 4) != hipSuccess)
+	    (!t8 && hipMalloc((void **) &k.w4, (size_t) t->nrows * 4) !=
+	     hipSuccess))
 	{
 		(void) hipGetLastError();
 		t->free_q1pack();
@@ -1354,9 +1367,20 @@ static gg_status q1_pack_prepare(Engine &e, Table *t, Pipeline *p)
 	}
 	k.sd_base = (int32_t) r.sdmin;
 	k.row_bound = q1_pack_row_bound(r.pmax, r.tmax);
+	k.tier = t8 ? 8 : 12;
+	k.qmax = r.qmax;
+	k.dmax = r.dmax;
+	if (t8)
+		k.lay = q1_pack8_layout(r);
 	{
 		Timed tm(e.stream);
-		hipError_t he = launch_q1_pack_build(
+		hipError_t he = t8 ? launch_q1_pack8_build(
+			e.stream, (const int32_t *) col[4],
+			(const uint8_t *) col[5], (const uint8_t *) col[6],
+			(const int64_t *) col[0], (const int64_t *) col[1],
+			(const int64_t *) col[2], (const int64_t *) col[3],
+			t->nrows, k.sd_base, k.lay, k.w8)
+			: launch_q1_pack_build(
 			e.stream, (const int32_t *) col[4],
 			(const uint8_t *) col[5], (const uint8_t *) col[6],
 			(const int64_t *) col[0], (const int64_t *) col[1],
@@ -1376,7 +1400,7 @@ static gg_status q1_pack_prepare(Engine &e, Table *t, Pipeline *p)
 		st.total_ms += ms;
 		st.rows_in += t->nrows;
 		st.rows_out += t->nrows;
-		st.hbm_bytes += t->nrows * (38 + 12);
+		st.hbm_bytes += t->nrows * (38 + k.tier);
 	}
 	k.state = 1;
 	return GG_OK;
@@ -1545,12 +1569,18 @@ static gg_status exec_q1(Pipeline *p, void *arena, size_t bytes,
 	GG_HIP(hipMemsetAsync(acc, 0, sizeof(*acc), e.stream));
 	/* the packed companion when the table has one (built at compile),
 	 * else the wide columns; the stat row keeps its name on both paths */
-	const bool packed = li->q1pack.state == 1 && q1_pack_enabled();
+	const Table::Q1Pack &k = li->q1pack;
+	const bool packed = k.state == 1 && q1_pack_enabled();
+	const bool packed8 = packed && k.tier == 8;
 	uint32_t c = 0;
 
 	p->stat(packed ? "path_q1_packed" : "path_q1_wide").launches++;
-	if (packed && !q1_pack_cutoff(p->desc.cutoff_date, li->q1pack.sd_base,
-				      &c))
+	if (packed8)
+		p->stat("path_q1_packed8").launches++;
+	if (packed &&
+	    !(packed8 ? q1_pack8_cutoff(p->desc.cutoff_date, k.sd_base,
+					k.lay.sd_mask, &c)
+	      : q1_pack_cutoff(p->desc.cutoff_date, k.sd_base, &c)))
 	{
 		/* cutoff below every shipdate: no row passes, nothing to
 		 * launch; the zeroed accumulator is the empty result */
@@ -1559,10 +1589,13 @@ static gg_status exec_q1(Pipeline *p, void *arena, size_t bytes,
 	{
 		Timed tm(e.stream);
 
-		if (packed)
-			GG_HIP(launch_q1_packed(e.stream, li->q1pack.w8,
-						li->q1pack.w4, li->nrows, c,
-						li->q1pack.row_bound, acc));
+		if (packed8)
+			GG_HIP(launch_q1_packed8(e.stream, k.w8, li->nrows, c,
+						 k.row_bound, k.lay, k.qmax,
+						 k.dmax, acc));
+		else if (packed)
+			GG_HIP(launch_q1_packed(e.stream, k.w8, k.w4, li->nrows,
+						c, k.row_bound, acc));
 		else
 			GG_HIP(launch_q1(e.stream, sd, rf, ls, q, pr, d, tx,
 					 li->nrows, p->desc.cutoff_date, acc));
@@ -1572,8 +1605,8 @@ static gg_status exec_q1(Pipeline *p, void *arena, size_t bytes,
 		st.launches++;
 		st.total_ms += ms;
 		st.rows_in += li->nrows;
-		/* 38 B/row wide, 12 B/row packed */
-		st.hbm_bytes += li->nrows * (packed ? 12 : 38);
+		/* 38 B/row wide, 12 or 8 B/row packed */
+		st.hbm_bytes += li->nrows * (packed ? k.tier : 38);
 	}
 
 	/* combine partial states (2-stage agg: cdbgroup.c:1245 /

@@ -16,6 +16,7 @@
 
 #include "../../include/engine_abi.h"
 #include "../../include/gg_result.h"
+#include "q1_pack.h"
 
 namespace gg
 {
@@ -84,17 +85,22 @@ struct Table
 	std::vector<Col> cols;
 
 	/* Packed Q1 companion (q1_pack.h; DESIGN.md "Packed Q1 companion"):
-	 * a 12 B/row copy of the seven Q1 columns, built at most once per
-	 * table (registered columns are immutable) and shared by every Q1
-	 * pipeline over it.  state 0 = not decided yet, 1 = w8/w4 valid,
-	 * -1 = the table is not eligible (remembered, never re-checked). */
+	 * a narrow copy of the seven Q1 columns in the narrowest tier the
+	 * table fits -- 8 B/row (w8 alone, laid out by `lay`) or 12 B/row (w8
+	 * and w4) -- built at most once per table (registered columns are
+	 * immutable) and shared by every Q1 pipeline over it.  state 0 = not
+	 * decided yet, 1 = the arrays of `tier` are valid, -1 = the table is
+	 * not eligible (remembered, never re-checked). */
 	struct Q1Pack
 	{
 		int state = 0;
+		int tier = 0;				/* 8 or 12 when state 1 */
 		unsigned long long *w8 = nullptr;	/* nrows u64 */
-		uint32_t *w4 = nullptr;			/* nrows u32 */
+		uint32_t *w4 = nullptr;		/* nrows u32, 12 B tier only */
 		int32_t sd_base = 0;			/* min(shipdate) */
 		uint64_t row_bound = 0;	/* q1_pack_row_bound(pmax, tmax) */
+		Q1Pack8Layout lay = {};			/* 8 B tier only */
+		long long qmax = 0, dmax = 0;	/* for Q1Pack8Fold */
 	};
 	Q1Pack q1pack;
 
@@ -444,6 +450,17 @@ hipError_t launch_q1_pack_build(hipStream_t s, const int32_t *shipdate,
 hipError_t launch_q1_packed(hipStream_t s, const unsigned long long *w8,
 			    const uint32_t *w4, int64_t n, uint32_t c,
 			    uint64_t row_bound, Q1DeviceAcc *acc);
+/* the 8 B tier: one u64 per row laid out by l; c is q1_pack8_cutoff's */
+hipError_t launch_q1_pack8_build(hipStream_t s, const int32_t *shipdate,
+				 const uint8_t *rflag, const uint8_t *lstatus,
+				 const int64_t *qty, const int64_t *price,
+				 const int64_t *disc, const int64_t *tax,
+				 int64_t n, int32_t sd_base,
+				 const Q1Pack8Layout &l, unsigned long long *w);
+hipError_t launch_q1_packed8(hipStream_t s, const unsigned long long *w,
+			     int64_t n, uint32_t c, uint64_t row_bound,
+			     const Q1Pack8Layout &l, long long qmax,
+			     long long dmax, Q1DeviceAcc *acc);
 
 hipError_t launch_count_shard(hipStream_t s, int64_t row_lo, int64_t n,
 			      int nseg, int seg, int which_table,

@@ -10,6 +10,8 @@
  *                     scaled-int arithmetic)
  *   k_q1_agg_packed   the same query over the 12 B/row companion that
  *                     k_q1_pack_build writes once per table (q1_pack.h)
+ *   k_q1_agg_packed8  the same over the companion's 8 B/row tier, written
+ *                     by k_q1_pack8_build when the table's ranges fit a u64
  *   k_build_* / k_probe_*  nodeHash.c:88–176/:905/:1002, nodeHashjoin.c:
  *                     78–510 (hash build/probe; open addressing instead
  *                     of chained buckets — GPU-native layout, same join
@@ -463,6 +465,266 @@ launch_q1_packed(hipStream_t s, const unsigned long long *w8,
 
 	hipLaunchKernelGGL(k_q1_agg_packed, dim3(grid), dim3(THREADS), 0, s,
 			   w8, w4, n, c, acc);
+	return hipGetLastError();
+}
+
+/* ------------------------------------------------------------------ */
+/* Q1 over the 8 B/row tier of the companion (q1_pack.h)               */
+/* ------------------------------------------------------------------ */
+
+__device__ inline unsigned long long
+q1_pack8_row(const Q1Pack8Layout &l, int32_t sd, uint8_t rf, uint8_t ls,
+	     int64_t q, int64_t p, int64_t d, int64_t t, int32_t sd_base)
+{
+	int fi = (rf == 'A') ? 0 : ((rf == 'N') ? 1 : ((rf == 'R') ? 2 : -1));
+	int si = (ls == 'F') ? 0 : ((ls == 'O') ? 1 : -1);
+	uint32_t code = (fi < 0 || si < 0) ? Q1P_BAD_CODE
+		: (uint32_t) (fi * 2 + si);
+
+	return q1_pack8_word(l, (uint32_t) sd - (uint32_t) sd_base, code,
+			     (uint32_t) d, (uint32_t) t, (uint32_t) q,
+			     (uint32_t) p);
+}
+
+/* k_q1_pack_build for the 8 B tier: the same eleven loads per 4 rows, two
+ * 16-byte stores. */
+__global__ __launch_bounds__(THREADS)
+void k_q1_pack8_build(const int32_t *__restrict__ shipdate,
+		      const uint8_t *__restrict__ rflag,
+		      const uint8_t *__restrict__ lstatus,
+		      const int64_t *__restrict__ qty,
+		      const int64_t *__restrict__ price,
+		      const int64_t *__restrict__ disc,
+		      const int64_t *__restrict__ tax,
+		      int64_t n, int32_t sd_base, Q1Pack8Layout l,
+		      unsigned long long *__restrict__ w)
+{
+	const int64_t nq = n / Q1P_ROWS;
+	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+	const int64_t gid = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+
+	for (int64_t qd = gid; qd < nq; qd += stride)
+	{
+		const int64_t i = qd * Q1P_ROWS;
+		q1_i32x4 sd = __builtin_nontemporal_load(
+			(const q1_i32x4 *) &shipdate[i]);
+		uint32_t rf = __builtin_nontemporal_load(
+			(const uint32_t *) &rflag[i]);
+		uint32_t ls = __builtin_nontemporal_load(
+			(const uint32_t *) &lstatus[i]);
+		q1_i64x2 q[2], p[2], d[2], t[2];
+		unsigned long long o[Q1P_ROWS];
+
+#pragma unroll
+		for (int h = 0; h < 2; h++)
+		{
+			q[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &qty[i + 2 * h]);
+			p[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &price[i + 2 * h]);
+			d[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &disc[i + 2 * h]);
+			t[h] = __builtin_nontemporal_load(
+				(const q1_i64x2 *) &tax[i + 2 * h]);
+		}
+#pragma unroll
+		for (int k = 0; k < Q1P_ROWS; k++)
+			o[k] = q1_pack8_row(l, sd[k], (uint8_t) (rf >> (8 * k)),
+					    (uint8_t) (ls >> (8 * k)),
+					    q[k >> 1][k & 1], p[k >> 1][k & 1],
+					    d[k >> 1][k & 1], t[k >> 1][k & 1],
+					    sd_base);
+		*(q1_u64x2 *) &w[i] = q1_u64x2{o[0], o[1]};
+		*(q1_u64x2 *) &w[i + 2] = q1_u64x2{o[2], o[3]};
+	}
+	if (gid == 0)
+		for (int64_t i = nq * Q1P_ROWS; i < n; i++)
+			w[i] = q1_pack8_row(l, shipdate[i], rflag[i], lstatus[i],
+					    qty[i], price[i], disc[i], tax[i],
+					    sd_base);
+}
+
+hipError_t
+launch_q1_pack8_build(hipStream_t s, const int32_t *shipdate,
+		      const uint8_t *rflag, const uint8_t *lstatus,
+		      const int64_t *qty, const int64_t *price,
+		      const int64_t *disc, const int64_t *tax, int64_t n,
+		      int32_t sd_base, const Q1Pack8Layout &l,
+		      unsigned long long *w)
+{
+	hipLaunchKernelGGL(k_q1_pack8_build, dim3(grid_for(q1_pack_quads(n))),
+			   dim3(THREADS), 0, s, shipdate, rflag, lstatus, qty,
+			   price, disc, tax, n, sd_base, l, w);
+	return hipGetLastError();
+}
+
+/* One row of the 8 B tier: the date predicate, then the bad-code rule of
+ * k_q1_agg_packed, then the adds into the lane's replica.  price is a u32
+ * (q1_pack_eligible), so disc4 is one 32x32->64 product and charge6 a
+ * 64x32 one.  FOLD: count, sum(disc) and sum(qty) go into slot 0 as one
+ * word (Q1Pack8Fold), four LDS adds instead of six. */
+template <bool FOLD>
+__device__ inline void
+q1_row8(unsigned long long *mine, const Q1Pack8Layout &l,
+	const Q1Pack8Fold &fo, uint32_t c, unsigned long long w,
+	unsigned long long &bad)
+{
+	const uint32_t code = q1_pack8_code(l, w);
+
+	if (q1_pack8_sd(l, w) > c)	/* l_shipdate <= cutoff */
+		return;
+	if (code > 5u)
+	{
+		bad = 1;
+		return;
+	}
+	unsigned long long *g = &mine[code * Q1_FIELDS];
+	const uint32_t d = q1_pack8_disc(l, w);
+	const uint32_t t = q1_pack8_tax(l, w);
+	const uint32_t q = q1_pack8_qty(l, w);
+	const uint32_t p = q1_pack8_price(l, w);
+	const unsigned long long disc4 = (unsigned long long) p * (100u - d);
+	const unsigned long long charge6 = disc4 * (100u + t);
+
+	if (FOLD)
+		atomicAdd(&g[0], ((unsigned long long) q << 32) |
+			  ((d << fo.d_shift) | 1u));
+	else
+	{
+		atomicAdd(&g[0], 1ull);
+		atomicAdd(&g[1], (unsigned long long) q);
+		atomicAdd(&g[3], (unsigned long long) d);
+	}
+	atomicAdd(&g[2], (unsigned long long) p);
+	atomicAdd(&g[4], disc4);
+	atomicAdd(&g[5], charge6);
+}
+
+/*
+ * Scan of the 8 B tier: k_q1_agg_packed with one array.  A lane takes 4
+ * consecutive rows (a quad) through two 16-byte nontemporal loads, and two
+ * of its quads per iteration with all four loads issued together: at
+ * 8 B/row one quad per lane in flight no longer covers the HBM latency.
+ * Which quads a lane takes is still the plain grid-stride assignment, so
+ * q1_pack_rows_per_block and q1_pack_grid hold as they are.  The date
+ * offset, the code and disc come out of a word's low dword.
+ */
+template <bool FOLD>
+__global__ __launch_bounds__(THREADS, 2)
+void k_q1_agg_packed8(const unsigned long long *__restrict__ wd, int64_t n,
+		      uint32_t c, Q1Pack8Layout l, Q1Pack8Fold fo,
+		      Q1DeviceAcc *acc)
+{
+	__shared__ unsigned long long lds[Q1_REPL * Q1_STRIDE];
+
+	for (int i = threadIdx.x; i < Q1_REPL * Q1_STRIDE; i += blockDim.x)
+		lds[i] = 0;
+	__syncthreads();
+
+	unsigned long long *mine =
+		&lds[(threadIdx.x & (Q1_REPL - 1)) * Q1_STRIDE];
+	const int64_t nq = n / Q1P_ROWS;
+	const int64_t stride = (int64_t) gridDim.x * blockDim.x;
+	const int64_t gid = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	unsigned long long bad = 0;
+	int64_t qd = gid;
+
+	for (; qd + stride < nq; qd += 2 * stride)
+	{
+		const unsigned long long *r0 = &wd[qd * Q1P_ROWS];
+		const unsigned long long *r1 = &wd[(qd + stride) * Q1P_ROWS];
+		q1_u64x2 v[4] = {
+			__builtin_nontemporal_load((const q1_u64x2 *) r0),
+			__builtin_nontemporal_load((const q1_u64x2 *) (r0 + 2)),
+			__builtin_nontemporal_load((const q1_u64x2 *) r1),
+			__builtin_nontemporal_load((const q1_u64x2 *) (r1 + 2)),
+		};
+
+#pragma unroll
+		for (int k = 0; k < 2 * Q1P_ROWS; k++)
+			q1_row8<FOLD>(mine, l, fo, c, v[k >> 1][k & 1], bad);
+	}
+	if (qd < nq)		/* the lane's last quad, when it has an odd count */
+	{
+		const unsigned long long *r0 = &wd[qd * Q1P_ROWS];
+		q1_u64x2 v[2] = {
+			__builtin_nontemporal_load((const q1_u64x2 *) r0),
+			__builtin_nontemporal_load((const q1_u64x2 *) (r0 + 2)),
+		};
+
+#pragma unroll
+		for (int k = 0; k < Q1P_ROWS; k++)
+			q1_row8<FOLD>(mine, l, fo, c, v[k >> 1][k & 1], bad);
+	}
+	/* the short tail (n % 4 rows): scalar loads in one thread, nothing
+	 * past row n - 1 is read */
+	if (gid == 0)
+		for (int64_t i = nq * Q1P_ROWS; i < n; i++)
+			q1_row8<FOLD>(mine, l, fo, c, wd[i], bad);
+	if (bad)
+		atomicOr(&acc->err, 1ull);
+	__syncthreads();
+
+	/* flush as k_q1_agg_packed does; a folded slot 0 is taken apart per
+	 * replica, before the replicas are summed */
+	for (int slot = threadIdx.x; slot < Q1_SLOTS; slot += blockDim.x)
+	{
+		const int g = slot / Q1_FIELDS;
+		const int fld = slot % Q1_FIELDS;
+		unsigned long long sum = 0;
+
+		if (fld > 5)
+			continue;
+		if (FOLD && (fld == 0 || fld == 1 || fld == 3))
+		{
+			/* count | sum(disc) << d_shift | sum(qty) << 32 */
+			const uint32_t sh = fld == 0 ? 0
+				: (fld == 3 ? fo.d_shift : 32);
+			const unsigned long long m = fld == 0
+				? (1ull << fo.d_shift) - 1
+				: (fld == 3 ? 0xFFFFFFFFull >> fo.d_shift
+				   : 0xFFFFFFFFull);
+
+#pragma unroll 1
+			for (int r = 0; r < Q1_REPL; r++)
+				sum += (lds[r * Q1_STRIDE + g * Q1_FIELDS] >> sh) & m;
+		}
+		else
+			for (int r = 0; r < Q1_REPL; r++)
+				sum += lds[r * Q1_STRIDE + slot];
+		if (!sum)
+			continue;
+		if (fld < 4)
+			atomicAdd(&acc->v[g][fld], sum);
+		else
+		{
+			/* disc4 -> v[4], v[5]; charge6 -> v[6], v[7] */
+			const int lo = fld == 4 ? 4 : 6;
+			unsigned long long old = atomicAdd(&acc->v[g][lo], sum);
+
+			if (old + sum < old)
+				atomicAdd(&acc->v[g][lo + 1], 1ull);
+		}
+	}
+}
+
+hipError_t
+launch_q1_packed8(hipStream_t s, const unsigned long long *w, int64_t n,
+		  uint32_t c, uint64_t row_bound, const Q1Pack8Layout &l,
+		  long long qmax, long long dmax, Q1DeviceAcc *acc)
+{
+	/* GG_Q1_GRID as for the 12 B tier; the fold is proven for the grid
+	 * that runs, six adds otherwise */
+	const char *gs = getenv("GG_Q1_GRID");
+	int grid = (int) q1_pack_grid(n, gs ? atoi(gs) : 0, row_bound);
+	Q1Pack8Fold fo = q1_pack8_fold(n, grid, qmax, dmax);
+
+	if (fo.on)
+		hipLaunchKernelGGL(k_q1_agg_packed8<true>, dim3(grid),
+				   dim3(THREADS), 0, s, w, n, c, l, fo, acc);
+	else
+		hipLaunchKernelGGL(k_q1_agg_packed8<false>, dim3(grid),
+				   dim3(THREADS), 0, s, w, n, c, l, fo, acc);
 	return hipGetLastError();
 }
 
