@@ -17,6 +17,12 @@ from .engine import (  # noqa: F401
     ATOM_RANGE,
     Engine,
     EngineError,
+    HAVING_IS_NULL,
+    HAVING_NEG_INF,
+    HAVING_NOT_NULL,
+    HAVING_NOT_RANGE,
+    HAVING_POS_INF,
+    HAVING_RANGE,
     JOIN_ANTI,
     JOIN_INNER,
     JOIN_LEFT,
@@ -26,10 +32,14 @@ from .engine import (  # noqa: F401
     PLAN_MAX_CLAUSES,
     PLAN_MAX_FILTERS,
     PLAN_MAX_FILTER_PREDS,
+    PLAN_MAX_HAVING_ATOMS,
+    PLAN_MAX_HAVING_CLAUSES,
+    PLAN_MAX_HAVING_TOTAL,
     PLAN_MAX_LIMIT,
     PLAN_MAX_ORDER,
     PLAN_MAX_WHERE_ATOMS,
     build_plan_desc,
+    build_plan_having,
     build_plan_where,
     pgdate,
     plan_group_bits,

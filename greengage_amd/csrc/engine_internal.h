@@ -16,6 +16,7 @@
 
 #include "../../include/engine_abi.h"
 #include "../../include/gg_result.h"
+#include "plan_having.h"
 #include "q1_pack.h"
 
 namespace gg
@@ -935,6 +936,22 @@ hipError_t launch_plan_topk_round(hipStream_t s, const PlanTopkDev &K,
 hipError_t launch_plan_topk_gather(hipStream_t s, const PlanTopkDev &K,
 				   const uint32_t *idx,
 				   unsigned long long *out);
+
+/* ---- device HAVING over the compacted group rows (plan_having.hip;
+ * PlanHavingDev and the row test are plan_having.h's) ----
+ * Appends the index of every row of rows[0..ng) that passes H to idx (ng
+ * entries of room, order unspecified) and adds their number to *ctr, which
+ * the caller zeroes.  ng < PL_TOPK_PAD. */
+hipError_t launch_plan_having_select(hipStream_t s, const PlanHavingDev &H,
+				     const unsigned long long *rows,
+				     uint64_t ng, int rowsz, uint32_t *idx,
+				     unsigned long long *ctr);
+/* out[j] = row idx[j] for j < ns, rowsz words each */
+hipError_t launch_plan_having_gather(hipStream_t s,
+				     const unsigned long long *rows,
+				     uint64_t ng, int rowsz,
+				     const uint32_t *idx, uint64_t ns,
+				     unsigned long long *out);
 
 /* plan.cpp */
 gg_status exec_plan(Pipeline *p, void *arena, size_t bytes,

@@ -93,6 +93,10 @@ struct PlanResolved
 	PlanWhereDev wh = {};
 	bool has_where = false;
 	bool where0 = false;
+	/* HAVING (gg_plan_having), its atoms resolved onto compacted-row
+	 * words; the device selection and the host filter both evaluate hv */
+	PlanHavingDev hv = {};
+	bool has_having = false;
 };
 
 static int coltype_width(gg_coltype t)
@@ -357,8 +361,65 @@ check_where(const gg_plan_desc *d, const gg_plan_where *w)
 	return GG_OK;
 }
 
+extern "C" size_t
+gg_engine_plan_having_size(void)
+{
+	return sizeof(gg_plan_having);
+}
+
+/* the HAVING's own shape (engine_abi.h gg_plan_having, "Errors") */
 static gg_status
-plan_compile(const gg_plan_desc *d, const gg_plan_where *w, gg_pipeline *out)
+check_having(const gg_plan_desc *d, const gg_plan_having *h)
+{
+	int total = 0;
+
+	if (h->nclauses < 0 || h->nclauses > GG_PLAN_MAX_HAVING_CLAUSES)
+		return fail(GG_ENOTSUP, "plan: %d having clauses (fall back to "
+			    "standard_ExecutorRun)", h->nclauses);
+	for (int c = 0; c < h->nclauses; c++)
+	{
+		const gg_plan_having_clause *C = &h->clauses[c];
+
+		if (C->natoms > GG_PLAN_MAX_HAVING_ATOMS)
+			return fail(GG_ENOTSUP, "plan: having clause %d has %d "
+				    "atoms (fall back to standard_ExecutorRun)", c,
+				    C->natoms);
+		if (C->natoms <= 0)
+			return fail(GG_EINVAL, "plan: having clause %d is an "
+				    "empty disjunction", c);
+		total += C->natoms;
+		for (int q = 0; q < C->natoms; q++)
+			if (C->atoms[q].kind < GG_HAVING_RANGE ||
+			    C->atoms[q].kind > GG_HAVING_NOT_NULL)
+				return fail(GG_ENOTSUP, "plan: having clause %d "
+					    "atom %d kind %d (fall back to "
+					    "standard_ExecutorRun)", c, q,
+					    C->atoms[q].kind);
+	}
+	if (total > GG_PLAN_MAX_HAVING_TOTAL)
+		return fail(GG_ENOTSUP, "plan: %d having atoms in all (fall "
+			    "back to standard_ExecutorRun)", total);
+	for (int c = 0; c < h->nclauses; c++)
+		for (int q = 0; q < h->clauses[c].natoms; q++)
+		{
+			int a = h->clauses[c].atoms[q].agg;
+
+			if (a < 0 || a >= d->naggs)
+				return fail(GG_EINVAL, "plan: having clause %d "
+					    "atom %d names aggregate %d, the plan "
+					    "has %d", c, q, a, d->naggs);
+			if (d->aggs[a].kind == GG_AGG_AVG)
+				return fail(GG_ENOTSUP, "plan: having clause %d "
+					    "atom %d: an AVG cannot be compared "
+					    "(fall back to standard_ExecutorRun)",
+					    c, q);
+		}
+	return GG_OK;
+}
+
+static gg_status
+plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
+	     const gg_plan_having *h, gg_pipeline *out)
 {
 	Engine &e = engine();
 
@@ -704,6 +765,39 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w, gg_pipeline *out)
 		R->has_where = true;
 	}
 
+	if (h)
+	{
+		/* the atoms, onto the words of a compacted row: what the
+		 * order's entries above read for the same aggregate */
+		int na = 0;
+
+		GG_TRY(check_having(d, h));
+		R->hv.nclauses = h->nclauses;
+		for (int c = 0; c < h->nclauses; c++)
+		{
+			R->hv.natoms[c] = (int8_t) h->clauses[c].natoms;
+			for (int q = 0; q < h->clauses[c].natoms; q++)
+			{
+				const gg_plan_having_atom *A =
+					&h->clauses[c].atoms[q];
+				const PlanResolved::OutAgg &O = R->outs[A->agg];
+				PlanHavingAtomDev &T = R->hv.atoms[na++];
+
+				T.lo_lo = A->lo_lo;
+				T.lo_hi = A->lo_hi;
+				T.hi_lo = A->hi_lo;
+				T.hi_hi = A->hi_hi;
+				T.kind = A->kind;
+				T.val = O.kind == GG_AGG_MIN ? PL_HV_MIN
+					: O.kind == GG_AGG_MAX ? PL_HV_MAX
+					: PL_HV_I128;
+				T.slot = (int8_t) O.slot;
+				T.cnt = (int8_t) (O.cnt < 0 ? 0 : O.cnt);
+			}
+		}
+		R->has_having = true;
+	}
+
 	Pipeline *p = new Pipeline();
 
 	p->desc = gg_pipeline_desc{};
@@ -717,7 +811,7 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w, gg_pipeline *out)
 extern "C" gg_status
 gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 {
-	return plan_compile(d, nullptr, out);
+	return plan_compile(d, nullptr, nullptr, out);
 }
 
 extern "C" gg_status
@@ -726,7 +820,17 @@ gg_engine_compile_plan_where(const gg_plan_desc *d, const gg_plan_where *w,
 {
 	/* no clauses: gg_engine_compile_plan exactly.  A count outside its
 	 * bounds is refused once the descriptor itself has been checked */
-	return plan_compile(d, w && w->nclauses != 0 ? w : nullptr, out);
+	return plan_compile(d, w && w->nclauses != 0 ? w : nullptr, nullptr,
+			    out);
+}
+
+extern "C" gg_status
+gg_engine_compile_plan_having(const gg_plan_desc *d, const gg_plan_where *w,
+			      const gg_plan_having *h, gg_pipeline *out)
+{
+	/* no clauses: gg_engine_compile_plan_where exactly */
+	return plan_compile(d, w && w->nclauses != 0 ? w : nullptr,
+			    h && h->nclauses != 0 ? h : nullptr, out);
 }
 
 static uint64_t next_pow2_pl(uint64_t v)
@@ -1533,11 +1637,14 @@ plan_topk_fits(Engine &e, const PlanResolved *R)
 
 /* 4'. device top-k (plan_topk.hip): tournament rounds over the compacted
  * rows until one tile is left, then only its first `limit` rows come to the
- * host.  ng > limit, so the last tile's head holds `limit` real rows. */
+ * host.  The first round's candidates are all ng rows, or, behind a device
+ * HAVING, the n0 row indices of its survivor list src0.  There are more
+ * candidates than `limit`, so the last tile's head holds `limit` real rows. */
 static gg_status
 plan_topk_device(Engine &e, Pipeline *p, const PlanResolved *R,
 		 const unsigned long long *dout, unsigned long long ng,
-		 std::vector<unsigned long long> &rows)
+		 std::vector<unsigned long long> &rows,
+		 const uint32_t *src0 = nullptr, uint64_t n0 = 0)
 {
 	const int rowsz = plan_rowsz(R);
 	const uint64_t limit = (uint64_t) R->limit;
@@ -1556,7 +1663,8 @@ plan_topk_device(Engine &e, Pipeline *p, const PlanResolved *R,
 
 	/* survivors of a round: its tiles x limit indices; the two buffers
 	 * alternate, the first round's output being the largest of each */
-	const uint64_t t0 = (ng + PL_TOPK_TILE - 1) / PL_TOPK_TILE;
+	const uint64_t ncand = src0 ? n0 : ng;
+	const uint64_t t0 = (ncand + PL_TOPK_TILE - 1) / PL_TOPK_TILE;
 	const uint64_t t1 = (t0 * limit + PL_TOPK_TILE - 1) / PL_TOPK_TILE;
 	uint32_t *buf[2] = {
 		(uint32_t *) p->sget("plan.topk.a", t0 * limit * 4),
@@ -1568,8 +1676,8 @@ plan_topk_device(Engine &e, Pipeline *p, const PlanResolved *R,
 		return fail(GG_ENOMEM, "plan top-k scratch");
 
 	Timed tm(e.stream);
-	const uint32_t *src = nullptr;
-	uint64_t n = ng;
+	const uint32_t *src = src0;
+	uint64_t n = ncand;
 	int rounds = 0;
 
 	for (;;)
@@ -1592,7 +1700,7 @@ plan_topk_device(Engine &e, Pipeline *p, const PlanResolved *R,
 
 		st.launches += rounds;
 		st.total_ms += ms;
-		st.rows_in += (int64_t) ng;
+		st.rows_in += (int64_t) ncand;
 		st.rows_out += (int64_t) limit;
 	}
 	rows.resize((size_t) limit * rowsz);
@@ -1640,6 +1748,67 @@ plan_bake(Engine &e, Pipeline *p, PlanResolved *R,
 	}
 }
 
+/* 3'. device HAVING (plan_having.hip): the indices of the compacted rows
+ * whose group passes, in *idx_p, and their number, the one word read back */
+static gg_status
+plan_having_device(Engine &e, Pipeline *p, const PlanResolved *R,
+		   const unsigned long long *dout, unsigned long long ng,
+		   unsigned long long *ctr, uint32_t **idx_p, uint64_t *ns_p)
+{
+	uint32_t *idx = (uint32_t *) p->sget("plan.having.idx",
+					      (size_t) ng * 4);
+	unsigned long long ns = 0;
+
+	if (!idx)
+		return fail(GG_ENOMEM, "plan having scratch");
+	Timed tm(e.stream);
+
+	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
+	GG_HIP(launch_plan_having_select(e.stream, R->hv, dout, ng,
+					 plan_rowsz(R), idx, ctr));
+	{
+		double ms = tm.stop();
+		KernelStatAcc &st = p->stat("plan_having");
+
+		GG_HIP(hipStreamSynchronize(e.stream));
+		GG_HIP(hipMemcpy(&ns, ctr, 8, hipMemcpyDeviceToHost));
+		st.launches++;
+		st.total_ms += ms;
+		st.rows_in += (int64_t) ng;
+		st.rows_out += (int64_t) ns;
+	}
+	if (ns > ng)
+		return fail(GG_ESTATE, "plan having overflow");
+	*idx_p = idx;
+	*ns_p = ns;
+	return GG_OK;
+}
+
+/* the survivors of a device HAVING, all ns of them, copied to the host */
+static gg_status
+plan_having_fetch(Engine &e, Pipeline *p, const PlanResolved *R,
+		  const unsigned long long *dout, unsigned long long ng,
+		  const uint32_t *idx, uint64_t ns,
+		  std::vector<unsigned long long> &rows)
+{
+	const int rowsz = plan_rowsz(R);
+
+	rows.resize((size_t) ns * rowsz);
+	if (!ns)
+		return GG_OK;
+	unsigned long long *out = (unsigned long long *)
+		p->sget("plan.having.out", rows.size() * 8);
+
+	if (!out)
+		return fail(GG_ENOMEM, "plan having scratch");
+	GG_HIP(launch_plan_having_gather(e.stream, dout, ng, rowsz, idx, ns,
+					 out));
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_HIP(hipMemcpy(rows.data(), out, rows.size() * 8,
+			 hipMemcpyDeviceToHost));
+	return GG_OK;
+}
+
 gg_status
 exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 {
@@ -1674,30 +1843,74 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		p->stat("path_plan_where").launches++;
 	GG_TRY(plan_build_joins(e, p, R, ctr));
 	GG_TRY(plan_scan_groups(e, p, R, ctr, &dout, &ng));
+	/* HAVING on the device: one segment (a group's partial states prove
+	 * nothing ahead of the combine) and, as for the top-k, more than the
+	 * handful of groups the second-stage bake wants whole on the host */
+	bool hvdev = false;
+	uint32_t *hidx = nullptr;
+	uint64_t ns = ng;	/* candidates of the order: groups, or survivors */
+
+	if (R->has_having)
+	{
+		/* read once per execute, like GG_PLAN_TOPK */
+		const char *hv = getenv("GG_PLAN_HAVING");
+
+		hvdev = e.cfg.n_segments == 1 && ng > 8 && ng < PL_TOPK_PAD &&
+			!(hv && !strcmp(hv, "host"));
+		p->stat(hvdev ? "path_plan_having_device"
+			: "path_plan_having_host").launches++;
+		if (hvdev)
+			GG_TRY(plan_having_device(e, p, R, dout, ng, ctr, &hidx,
+						  &ns));
+	}
 	if (ordered)
 	{
 		/* read once per execute, like GG_PLAN_BAKE */
 		const char *tk = getenv("GG_PLAN_TOPK");
 
 		/* ng > 8 leaves the small group sets, which the second-stage
-		 * bake wants whole on the host, to the host path */
+		 * bake wants whole on the host, to the host path; so does a
+		 * HAVING the host evaluates, whose survivors only it knows */
 		topk = e.cfg.n_segments == 1 && R->limit > 0 &&
 			R->limit <= GG_PLAN_MAX_LIMIT &&
-			ng > (unsigned long long) R->limit && ng > 8 &&
+			ns > (uint64_t) R->limit && ng > 8 &&
 			ng < PL_TOPK_PAD && !(tk && !strcmp(tk, "host")) &&
-			plan_topk_fits(e, R);
+			(hvdev || !R->has_having) && plan_topk_fits(e, R);
 		p->stat(topk ? "path_plan_topk_device"
 			: "path_plan_topk_host").launches++;
 	}
 	if (topk)
-		GG_TRY(plan_topk_device(e, p, R, dout, ng, rows));
+		GG_TRY(plan_topk_device(e, p, R, dout, ng, rows, hidx, ns));
+	else if (hvdev)
+		GG_TRY(plan_having_fetch(e, p, R, dout, ng, hidx, ns, rows));
 	else
 		GG_TRY(plan_fetch_rows(R, dout, ng, rows));
 	if (e.cfg.n_segments > 1)
 		GG_TRY(plan_combine_segments(e, p, R, dout, rows));
+	if (R->has_having && !hvdev)
+	{
+		/* the host's HAVING: the bake first, from the FULL group set
+		 * (a later baked execute must still find every group), then
+		 * the row test the device runs */
+		const int rowsz = plan_rowsz(R);
+		size_t keep = 0;
+
+		plan_bake(e, p, R, rows);
+		for (size_t i = 0; i < rows.size() / rowsz; i++)
+			if (plan_having_row(R->hv, &rows[i * rowsz]))
+			{
+				if (keep != i)
+					std::memmove(&rows[keep * rowsz],
+						     &rows[i * rowsz],
+						     (size_t) rowsz * 8);
+				keep++;
+			}
+		rows.resize(keep * rowsz);
+	}
 	GG_TRY(plan_write_arena(R, rows, arena, bytes, written));
-	/* the bake wants the whole group set; a top-k left only its head */
-	if (!topk)
+	/* the bake wants the whole group set: a top-k left only its head, a
+	 * device HAVING only its survivors, and the host's HAVING baked above */
+	if (!topk && !R->has_having)
 		plan_bake(e, p, R, rows);
 	return GG_OK;
 }

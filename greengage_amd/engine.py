@@ -119,6 +119,33 @@ class _PlanWhere(ctypes.Structure):
                 ("nclauses", ctypes.c_int)]
 
 
+PLAN_MAX_HAVING_CLAUSES = 4   # GG_PLAN_MAX_HAVING_CLAUSES
+PLAN_MAX_HAVING_ATOMS = 4     # GG_PLAN_MAX_HAVING_ATOMS
+PLAN_MAX_HAVING_TOTAL = 8     # GG_PLAN_MAX_HAVING_TOTAL
+# gg_plan_havingkind (engine_abi.h)
+HAVING_RANGE, HAVING_NOT_RANGE = 0, 1
+HAVING_IS_NULL, HAVING_NOT_NULL = 2, 3
+# signed 128-bit bounds of a HAVING atom; as lo / hi they mean "no test"
+HAVING_NEG_INF = -(1 << 127)
+HAVING_POS_INF = (1 << 127) - 1
+
+
+class _PlanHavingAtom(ctypes.Structure):
+    _fields_ = [("lo_lo", U64), ("lo_hi", I64), ("hi_lo", U64),
+                ("hi_hi", I64), ("kind", ctypes.c_int8),
+                ("agg", ctypes.c_int8)]
+
+
+class _PlanHavingClause(ctypes.Structure):
+    _fields_ = [("atoms", _PlanHavingAtom * PLAN_MAX_HAVING_ATOMS),
+                ("natoms", ctypes.c_int)]
+
+
+class _PlanHaving(ctypes.Structure):
+    _fields_ = [("clauses", _PlanHavingClause * PLAN_MAX_HAVING_CLAUSES),
+                ("nclauses", ctypes.c_int)]
+
+
 NEG_INF = -(1 << 63)          # one-sided range bounds
 POS_INF = (1 << 63) - 1
 PLAN_NULL_KEY = -(1 << 63) + 1
@@ -386,6 +413,115 @@ def build_plan_where(joins=(), where=()):
     return w
 
 
+def build_plan_having(aggs=(), having=()):
+    """The gg_plan_having (engine_abi.h) of a plan's HAVING: `having` holds
+    clauses, which are ANDed, over the values of the plan's aggregates
+    `aggs` (build_plan_desc's list).  Pure: calls neither the library nor a
+    GPU.
+
+    A clause is a list of atoms (ORed), or one atom; `a` is an aggregate's
+    index in `aggs`:
+      ("range", a, lo, hi)         lo <= v < hi
+      ("not_range", a, lo, hi)     v < lo or v >= hi
+      ("cmp", a, op, v)            op in < <= = <> > >=, as a range with
+                                   HAVING_NEG_INF / HAVING_POS_INF for the
+                                   open side
+      ("in", a, [v, ...])          expands to equalities inside its clause
+      ("is_null", a) | ("not_null", a)
+    Values are signed 128-bit integers in the aggregate's own scaled units.
+    HAVING_NEG_INF as lo and HAVING_POS_INF as hi mean "no test" (so an hi of
+    HAVING_POS_INF does not exclude that one value).  A MIN or MAX of a group
+    without a non-NULL input is NULL: ranges over it are not true.
+    More than PLAN_MAX_HAVING_CLAUSES clauses, PLAN_MAX_HAVING_ATOMS atoms in
+    a clause or PLAN_MAX_HAVING_TOTAL in all, an unknown atom, an aggregate
+    index outside `aggs`, an AVG, a bound outside 128 bits or a v + 1 that
+    leaves them raise ValueError."""
+    def is_avg(spec):
+        if isinstance(spec, (tuple, list)) and spec and spec[0] == "filter":
+            spec = spec[1]
+        return isinstance(spec, (tuple, list)) and bool(spec) and \
+            spec[0] == "avg"
+
+    def agg(a):
+        a = int(a)
+        if not 0 <= a < len(aggs):
+            raise ValueError(f"having names aggregate {a}, the plan has "
+                             f"{len(aggs)}")
+        if is_avg(aggs[a]):
+            raise ValueError(f"having names aggregate {a}, an AVG")
+        return a
+
+    def bound(v):
+        v = int(v)
+        if not HAVING_NEG_INF <= v <= HAVING_POS_INF:
+            raise ValueError(f"having bound {v} outside 128 bits")
+        return v
+
+    def succ(v):
+        v = bound(v)
+        if v == HAVING_POS_INF:
+            raise ValueError(f"having value {v}: v + 1 leaves 128 bits")
+        return v + 1
+
+    def atoms_of(t):
+        """(kind, agg, lo, hi) per atom"""
+        tag = t[0]
+        if tag == "range":
+            return [(HAVING_RANGE, agg(t[1]), bound(t[2]), bound(t[3]))]
+        if tag == "not_range":
+            return [(HAVING_NOT_RANGE, agg(t[1]), bound(t[2]), bound(t[3]))]
+        if tag == "in":
+            return [(HAVING_RANGE, agg(t[1]), bound(v), succ(v))
+                    for v in t[2]]
+        if tag == "cmp":
+            a, op, v = agg(t[1]), t[2], t[3]
+            if op == "<":
+                return [(HAVING_RANGE, a, HAVING_NEG_INF, bound(v))]
+            if op == "<=":
+                return [(HAVING_RANGE, a, HAVING_NEG_INF, succ(v))]
+            if op == "=":
+                return [(HAVING_RANGE, a, bound(v), succ(v))]
+            if op == "<>":
+                return [(HAVING_NOT_RANGE, a, bound(v), succ(v))]
+            if op == ">":
+                return [(HAVING_RANGE, a, succ(v), HAVING_POS_INF)]
+            if op == ">=":
+                return [(HAVING_RANGE, a, bound(v), HAVING_POS_INF)]
+            raise ValueError(f"unknown having comparison {op!r}")
+        if tag == "is_null":
+            return [(HAVING_IS_NULL, agg(t[1]), 0, 0)]
+        if tag == "not_null":
+            return [(HAVING_NOT_NULL, agg(t[1]), 0, 0)]
+        raise ValueError(f"unknown having atom {t!r}")
+
+    def is_atom(c):
+        return isinstance(c, tuple) and len(c) > 0 and isinstance(c[0], str)
+
+    clauses = [atoms_of(cl) if is_atom(cl)
+               else [t for a in cl for t in atoms_of(a)] for cl in having]
+    if len(clauses) > PLAN_MAX_HAVING_CLAUSES:
+        raise ValueError(
+            f"a plan holds at most {PLAN_MAX_HAVING_CLAUSES} having clauses")
+    if sum(len(atoms) for atoms in clauses) > PLAN_MAX_HAVING_TOTAL:
+        raise ValueError(
+            f"a plan holds at most {PLAN_MAX_HAVING_TOTAL} having atoms")
+    h = _PlanHaving()
+    h.nclauses = len(clauses)
+    m64 = (1 << 64) - 1
+    for c, atoms in enumerate(clauses):
+        if not 0 < len(atoms) <= PLAN_MAX_HAVING_ATOMS:
+            raise ValueError(
+                f"having clause {c}: a clause holds 1 to "
+                f"{PLAN_MAX_HAVING_ATOMS} atoms")
+        h.clauses[c].natoms = len(atoms)
+        for q, (kind, a, lo, hi) in enumerate(atoms):
+            t = h.clauses[c].atoms[q]
+            t.kind, t.agg = kind, a
+            t.lo_lo, t.lo_hi = lo & m64, lo >> 64
+            t.hi_lo, t.hi_hi = hi & m64, hi >> 64
+    return h
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("launches", I64),
                 ("total_ms", ctypes.c_double), ("rows_in", I64),
@@ -454,6 +590,12 @@ def _load():
         ctypes.POINTER(I32)]
     lib.gg_engine_plan_where_size.argtypes = []
     lib.gg_engine_plan_where_size.restype = ctypes.c_size_t
+    lib.gg_engine_compile_plan_having.restype = ctypes.c_int
+    lib.gg_engine_compile_plan_having.argtypes = [
+        ctypes.POINTER(_PlanDesc), ctypes.POINTER(_PlanWhere),
+        ctypes.POINTER(_PlanHaving), ctypes.POINTER(I32)]
+    lib.gg_engine_plan_having_size.argtypes = []
+    lib.gg_engine_plan_having_size.restype = ctypes.c_size_t
     lib.gg_engine_plan_desc_size.argtypes = []
     lib.gg_engine_plan_desc_size.restype = ctypes.c_size_t
     lib.gg_engine_plan_topk_tile.argtypes = []
@@ -730,16 +872,23 @@ class Engine:
 
     # ---- generalized pipeline descriptor (v2) ----
     def compile_plan(self, scan_table, preds=(), joins=(), group_cols=(),
-                     aggs=(), order_by=(), limit=0, est_groups=0, where=()):
+                     aggs=(), order_by=(), limit=0, est_groups=0, where=(),
+                     having=()):
         """Compile a compositional plan (engine_abi.h gg_plan_desc); the
-        arguments are build_plan_desc's, and `where` (with the join specs'
-        "where" keys) build_plan_where's.  A plan without a clause goes
-        through gg_engine_compile_plan as ever."""
+        arguments are build_plan_desc's, `where` (with the join specs'
+        "where" keys) build_plan_where's and `having` build_plan_having's.
+        A plan without a clause goes through gg_engine_compile_plan as
+        ever, one without a HAVING clause takes the calls it always took."""
         d, kinds = build_plan_desc(scan_table, preds, joins, group_cols,
                                    aggs, order_by, limit, est_groups)
         w = build_plan_where(joins, where)
+        hv = build_plan_having(aggs, having)
         h = I32()
-        if w.nclauses:
+        if hv.nclauses:
+            _check(lib().gg_engine_compile_plan_having(
+                ctypes.byref(d), ctypes.byref(w) if w.nclauses else None,
+                ctypes.byref(hv), ctypes.byref(h)), "compile_plan")
+        elif w.nclauses:
             _check(lib().gg_engine_compile_plan_where(
                 ctypes.byref(d), ctypes.byref(w), ctypes.byref(h)),
                 "compile_plan")

@@ -955,6 +955,110 @@ gg_status gg_engine_compile_plan_where(const gg_plan_desc *desc,
 /* sizeof(gg_plan_where), for bindings; needs no GPU */
 size_t gg_engine_plan_where_size(void);
 
+/* HAVING: a qual over the plan's aggregates, the qual of the Agg node
+ * (nodeAgg.c: ExecQual over the projected aggregates decides whether a
+ * finished group is emitted).  Like gg_plan_where it travels BESIDE the
+ * descriptor, which keeps its layout.
+ *
+ * Form.  The form of gg_plan_where: conjunctive normal form, negation only
+ * in the atoms, an atom either true or not true; the two-valued argument
+ * given there holds word for word.
+ *   having = clauses[0] AND clauses[1] AND ...
+ *   clause = atoms[0] OR atoms[1] OR ...
+ *   atom   = one of gg_plan_havingkind over the value v of descriptor
+ *            aggregate `agg`
+ *
+ * Value.  v is what an order key over the same aggregate compares
+ * (gg_plan_order, what = 1):
+ *   COUNT(*), COUNT(col), SUM   the signed 128-bit accumulator, never NULL.
+ *                               A SUM with no non-NULL input reads as 0, the
+ *                               arena's convention; a caller who needs SQL's
+ *                               NULL there ANDs a clause COUNT(col) >= 1
+ *                               under the same filter.
+ *   MIN, MAX                    the decoded int64 widened to 128 bits; NULL
+ *                               when the group's non-NULL count N is 0.
+ *   AVG                         GG_ENOTSUP at compile, for the reason an AVG
+ *                               order key is refused.
+ *
+ * Comparison.  RANGE and NOT_RANGE over a NULL are not true.  IS_NULL is true
+ * exactly when v is NULL (never for COUNT and SUM); NOT_NULL is its
+ * complement.  Bounds are literal signed 128-bit values, lo inclusive and hi
+ * exclusive: RANGE is lo <= v < hi, except that lo == INT128_MIN means no
+ * lower test and hi == INT128_MAX no upper test (so v = INT128_MAX is inside
+ * [x, INT128_MAX)); NOT_RANGE is the exact complement of RANGE on non-NULL
+ * values, whatever lo and hi are (lo >= hi: RANGE is empty).  Constants are
+ * in the aggregate's own scaled-integer units: the caller applies the scale,
+ * as for arena values.  Comparing one aggregate against another, and atoms
+ * over group keys, are out of scope: a group key belongs in the WHERE.
+ *
+ * Placement.  HAVING runs after aggregation, aggregate FILTERs included, and
+ * after the cross-segment combine (a group's partial states prove nothing on
+ * one segment); it runs before ORDER BY and LIMIT.  n_groups = min(surviving
+ * groups, limit), or the survivor count without a limit, and the arena needs
+ * room only for the emitted rows.  With ngroup == 0 the plan's one row is
+ * emitted iff it passes: n_groups == 0 with 16 bytes written is a valid
+ * result.
+ *
+ * With one segment and more than 8 groups the qual is evaluated on the
+ * device, over the compacted group rows, and only the survivors (or, under a
+ * limit the device top-k serves, the first `limit` of them) are copied back;
+ * otherwise the groups are copied out, combined, and filtered on the host by
+ * the same row test.  GG_PLAN_HAVING=host in the environment forces the host
+ * path.  Stat rows: path_plan_having_device or path_plan_having_host counts
+ * one per execute of a plan with HAVING, and the kernel row plan_having has
+ * rows_in = groups and rows_out = survivors of the device path.
+ *
+ * having == NULL or nclauses == 0 is gg_engine_compile_plan_where exactly:
+ * same validation, same kernels, same generated program text, no new stat
+ * rows.
+ *
+ * Errors.  The descriptor and the WHERE are validated first.  GG_ENOTSUP:
+ * nclauses outside [0, GG_PLAN_MAX_HAVING_CLAUSES], natoms >
+ * GG_PLAN_MAX_HAVING_ATOMS, more than GG_PLAN_MAX_HAVING_TOTAL atoms in all,
+ * an unknown kind, an atom over an AVG.  GG_EINVAL: natoms <= 0, agg outside
+ * [0, naggs). */
+#define GG_PLAN_MAX_HAVING_CLAUSES 4	/* per gg_plan_having */
+#define GG_PLAN_MAX_HAVING_ATOMS   4	/* per clause */
+#define GG_PLAN_MAX_HAVING_TOTAL   8	/* per gg_plan_having, all clauses */
+
+typedef enum gg_plan_havingkind
+{
+	GG_HAVING_RANGE = 0,	/* lo <= v < hi */
+	GG_HAVING_NOT_RANGE = 1,	/* v < lo || v >= hi */
+	GG_HAVING_IS_NULL = 2,	/* v IS NULL */
+	GG_HAVING_NOT_NULL = 3	/* v IS NOT NULL */
+} gg_plan_havingkind;
+
+typedef struct gg_plan_having_atom
+{
+	uint64_t lo_lo;		/* signed 128-bit lo, inclusive */
+	int64_t lo_hi;
+	uint64_t hi_lo;		/* signed 128-bit hi, exclusive */
+	int64_t hi_hi;
+	int8_t kind;		/* gg_plan_havingkind */
+	int8_t agg;		/* descriptor aggregate index */
+} gg_plan_having_atom;
+
+typedef struct gg_plan_having_clause	/* atoms[0] OR atoms[1] OR ... */
+{
+	gg_plan_having_atom atoms[GG_PLAN_MAX_HAVING_ATOMS];
+	int natoms;
+} gg_plan_having_clause;
+
+typedef struct gg_plan_having		/* clauses[0] AND clauses[1] ... */
+{
+	gg_plan_having_clause clauses[GG_PLAN_MAX_HAVING_CLAUSES];
+	int nclauses;
+} gg_plan_having;
+
+gg_status gg_engine_compile_plan_having(const gg_plan_desc *desc,
+					const gg_plan_where *where,
+					const gg_plan_having *having,
+					gg_pipeline *out);
+
+/* sizeof(gg_plan_having), for bindings; needs no GPU */
+size_t gg_engine_plan_having_size(void);
+
 /* Rows per tile of the device top-k's tournament (a power of two, at least
  * 2 * GG_PLAN_MAX_LIMIT): group counts around it are where the selection
  * takes another round.  A constant of the build; needs no GPU. */
