@@ -23,9 +23,6 @@
 namespace gg
 {
 
-#define GG_TRY(expr) \
-	do { gg_status _s = (expr); if (_s != GG_OK) return _s; } while (0)
-
 static_assert(sizeof(ncclUniqueId) <= 128, "comm id fits 128 bytes");
 
 /*

@@ -49,19 +49,6 @@ Engine &engine()
 	return e;
 }
 
-/* comm.cpp */
-gg_status comm_make_id(void *out_id128);
-gg_status comm_init(const void *id128);
-gg_status comm_destroy();
-bool comm_ready();
-gg_status comm_allgather_u64(const void *dev_send, void *dev_recv,
-			     size_t count);
-gg_status comm_alltoallv_i64(const int64_t *send_base,
-			     const unsigned long long *send_offs,
-			     const unsigned long long *send_cnts, int64_t *recv_base,
-			     const unsigned long long *recv_offs,
-			     const unsigned long long *recv_cnts);
-
 static uint64_t next_pow2(uint64_t v)
 {
 	uint64_t p = 1024;	/* floor tuned for hash-table slot counts */
@@ -96,9 +83,6 @@ static size_t coltype_size(gg_coltype t)
 	return 0;
 }
 
-#define GG_TRY(expr) \
-	do { gg_status _s = (expr); if (_s != GG_OK) return _s; } while (0)
-
 /* device scratch counter helpers */
 static gg_status dev_counter(unsigned long long **p)
 {
@@ -115,6 +99,18 @@ static gg_status read_counter(unsigned long long *p, unsigned long long *out)
 	return GG_OK;
 }
 
+/* the counted launch: zero the device counter, launch() (which returns the
+ * launcher's hipError_t), wait, read the counter back */
+template <typename F>
+static gg_status run_counted(hipStream_t s, unsigned long long *ctr,
+			     unsigned long long *out, F launch)
+{
+	GG_HIP(hipMemsetAsync(ctr, 0, 8, s));
+	GG_HIP(launch());
+	GG_HIP(hipStreamSynchronize(s));
+	return read_counter(ctr, out);
+}
+
 /* max over an immutable registered column, cached per pipeline */
 static gg_status
 cached_max_i64(Engine &e, Pipeline *p, const int64_t *col, int64_t n,
@@ -127,10 +123,9 @@ cached_max_i64(Engine &e, Pipeline *p, const int64_t *col, int64_t n,
 			*out = kv.second;
 			return GG_OK;
 		}
-	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-	GG_HIP(launch_max_i64(e.stream, col, n, ctr));
-	GG_HIP(hipStreamSynchronize(e.stream));
-	GG_TRY(read_counter(ctr, out));
+	GG_TRY(run_counted(e.stream, ctr, out, [&] {
+		return launch_max_i64(e.stream, col, n, ctr);
+	}));
 	p->maxk_cache.push_back({{(const void *) col, n}, *out});
 	return GG_OK;
 }
@@ -1471,6 +1466,79 @@ extern "C" gg_status gg_engine_drop_pipeline(gg_pipeline h)
 	return GG_OK;
 }
 
+/* ---------------- helpers shared by the Q3 / Q5 executors ---------------- */
+
+/* Dense direct-map length for a key column (nodeHash.c:450 sizing decision
+ * analog): max(key) + 1 when the keys are dense enough (max <= 8x rows) for
+ * a direct map to beat a hash table, else 0.  The max is cached per
+ * pipeline. */
+static gg_status dense_key_len(Engine &e, Pipeline *p, const int64_t *col,
+			       int64_t nrows, unsigned long long *ctr,
+			       int64_t *dlen)
+{
+	unsigned long long maxk = 0;
+
+	GG_TRY(cached_max_i64(e, p, col, nrows, ctr, &maxk));
+	*dlen = nrows > 0 && maxk > 0 &&
+		maxk <= (unsigned long long) (8 * nrows + 16)
+		? (int64_t) maxk + 1 : 0;
+	return GG_OK;
+}
+
+/* which arrays a DeviceHashTable carries beside its keys */
+enum
+{
+	HT_PAYLOAD = 1,
+	HT_REV = 2,
+	HT_BLOOM = 4
+};
+
+/* Size and zero a hash table in the scratch buffers `prefix`.keys / .pay /
+ * .rev / .bloom.  Keys, rev and bloom start at zero; payload slots need NO
+ * init: a slot is read only after its key was installed, and the insert
+ * that installs the key stores the payload. */
+static gg_status hash_table_alloc(Pipeline *p, const char *prefix,
+				  uint64_t nslots, int want,
+				  DeviceHashTable *t)
+{
+	hipStream_t s = engine().stream;
+	std::string pre(prefix);
+	bool ok;
+
+	*t = DeviceHashTable();
+	t->nslots = nslots;
+	t->keys = (unsigned long long *)
+		p->sget((pre + ".keys").c_str(), nslots * 8);
+	ok = t->keys != nullptr;
+	if (want & HT_PAYLOAD)
+	{
+		t->payload = (unsigned long long *)
+			p->sget((pre + ".pay").c_str(), nslots * 8);
+		ok = ok && t->payload;
+	}
+	if (want & HT_REV)
+	{
+		t->rev = (unsigned long long *)
+			p->sget((pre + ".rev").c_str(), nslots * 8);
+		ok = ok && t->rev;
+	}
+	if (want & HT_BLOOM)
+	{
+		t->bloom_words = nslots / 8 < 1024 ? 1024 : nslots / 8;
+		t->bloom = (unsigned long long *)
+			p->sget((pre + ".bloom").c_str(), t->bloom_words * 8);
+		ok = ok && t->bloom;
+	}
+	if (!ok)
+		return fail(GG_ENOMEM, "%s table", prefix);
+	GG_HIP(hipMemsetAsync(t->keys, 0, nslots * 8, s));
+	if (t->rev)
+		GG_HIP(hipMemsetAsync(t->rev, 0, nslots * 8, s));
+	if (t->bloom)
+		GG_HIP(hipMemsetAsync(t->bloom, 0, t->bloom_words * 8, s));
+	return GG_OK;
+}
+
 /* ---------------- execution: SUMPRICE ---------------- */
 
 static gg_status exec_sumprice(Pipeline *p, void *arena, size_t bytes,
@@ -1496,13 +1564,8 @@ static gg_status exec_sumprice(Pipeline *p, void *arena, size_t bytes,
 
 		GG_HIP(launch_sumprice(e.stream, sd, pr, li->nrows,
 				       p->desc.cutoff_date, acc));
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("sumprice");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += li->nrows;
-		st.hbm_bytes += li->nrows * 12;
+		p->stat("sumprice").add(tm.stop(), li->nrows, 0,
+					li->nrows * 12);
 	}
 	SumPriceAcc h;
 
@@ -1515,16 +1578,10 @@ static gg_status exec_sumprice(Pipeline *p, void *arena, size_t bytes,
 	{
 		if (!comm_ready())
 			return fail(GG_ESTATE, "multi-segment without comm");
-		unsigned long long *dbuf;
-		std::vector<unsigned long long> all(2 * e.cfg.n_segments);
+		static_assert(sizeof(SumPriceAcc) == 16, "acc layout");
+		std::vector<unsigned long long> all;
 
-		GG_HIP(hipMalloc((void **) &dbuf,
-				 (2 + 2 * e.cfg.n_segments) * 8));
-		GG_HIP(hipMemcpy(dbuf, &h, 16, hipMemcpyHostToDevice));
-		GG_TRY(comm_allgather_u64(dbuf, dbuf + 2, 2));
-		GG_HIP(hipMemcpy(all.data(), dbuf + 2, all.size() * 8,
-				 hipMemcpyDeviceToHost));
-		(void) hipFree(dbuf);
+		GG_TRY(allgather_host_u64(p, "sp.gather", &h.sum_c, 2, all));
 		sum = 0;
 		cnt = 0;
 		for (int r = 0; r < e.cfg.n_segments; r++)
@@ -1599,14 +1656,9 @@ static gg_status exec_q1(Pipeline *p, void *arena, size_t bytes,
 		else
 			GG_HIP(launch_q1(e.stream, sd, rf, ls, q, pr, d, tx,
 					 li->nrows, p->desc.cutoff_date, acc));
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("q1_agg");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += li->nrows;
 		/* 38 B/row wide, 12 or 8 B/row packed */
-		st.hbm_bytes += li->nrows * (packed ? k.tier : 38);
+		p->stat("q1_agg").add(tm.stop(), li->nrows, 0,
+				      li->nrows * (packed ? k.tier : 38));
 	}
 
 	/* combine partial states (2-stage agg: cdbgroup.c:1245 /
@@ -1621,15 +1673,9 @@ static gg_status exec_q1(Pipeline *p, void *arena, size_t bytes,
 	{
 		if (!comm_ready())
 			return fail(GG_ESTATE, "multi-segment without comm");
-		unsigned long long *gbuf;
-
-		GG_HIP(hipMalloc((void **) &gbuf, 49 * 8 * (size_t) (nseg + 1)));
-		GG_HIP(hipMemcpy(gbuf, acc, 49 * 8, hipMemcpyDeviceToDevice));
-		GG_TRY(comm_allgather_u64(gbuf, gbuf + 49, 49));
-		parts.resize(49 * (size_t) nseg);
-		GG_HIP(hipMemcpy(parts.data(), gbuf + 49, parts.size() * 8,
-				 hipMemcpyDeviceToHost));
-		(void) hipFree(gbuf);
+		GG_TRY(allgather_host_u64(p, "q1.gather",
+					  (const unsigned long long *) acc, 49,
+					  parts, hipMemcpyDeviceToDevice));
 	}
 	else
 	{
@@ -1705,129 +1751,26 @@ struct Q3TopkCmp
 	}
 };
 
-static gg_status exec_q3(Pipeline *p, void *arena, size_t bytes,
-			 size_t *written)
+/* what the steps of one Q3 execute hand each other */
+struct Q3State
 {
-	Engine &e = engine();
-	Table *li = get_table(p->desc.lineitem);
-	Table *od = get_table(p->desc.orders);
-	Table *cu = get_table(p->desc.customer);
-	int nseg = e.cfg.n_segments;
-	int me = e.cfg.segment_id;
-	int64_t k = p->desc.limit_k > 0 ? p->desc.limit_k : 10;
-	/* the Motion-exchange path normally runs for nseg > 1; the env
-	 * knob forces it at nseg == 1 (self-loopback over RCCL) so the
-	 * whole redistribute plumbing is testable on one GPU */
-	bool exch = nseg > 1 || getenv("GG_FORCE_EXCHANGE") != nullptr;
+	Pipeline *p;
+	Table *li, *od, *cu;
+	int64_t k;
+	bool exch;
+	int32_t cutoff;
+	uint8_t segcode;
+	const int64_t *c_ck, *o_ok, *o_ck, *l_ok, *l_pc, *l_dc;
+	const uint8_t *c_ms;
+	const int32_t *o_dt, *o_pr, *l_sd;
+	unsigned long long *ctr;	/* 8-byte device counter */
 
-	if (bytes < sizeof(gg_q3_result_hdr) +
-	    (size_t) k * sizeof(gg_q3_result_row))
-		return fail(GG_EINVAL, "arena too small");
-	if (k > 1000)
-		return fail(GG_ENOTSUP, "LIMIT > 1000 not supported in v1");
-
-	const int64_t *c_ck = (const int64_t *) cu->col("custkey");
-	const uint8_t *c_ms = (const uint8_t *) cu->col("mktseg");
-	const int64_t *o_ok = (const int64_t *) od->col("orderkey");
-	const int64_t *o_ck = (const int64_t *) od->col("custkey");
-	const int32_t *o_dt = (const int32_t *) od->col("orderdate");
-	const int32_t *o_pr = (const int32_t *) od->col("shippriority");
-	const int64_t *l_ok = (const int64_t *) li->col("orderkey");
-	const int32_t *l_sd = (const int32_t *) li->col("shipdate");
-	const int64_t *l_pc = (const int64_t *) li->col("price");
-	const int64_t *l_dc = (const int64_t *) li->col("disc");
-
-	if (!c_ck || !c_ms || !o_ok || !o_ck || !o_dt || !o_pr || !l_ok ||
-	    !l_sd || !l_pc || !l_dc)
-		return fail(GG_EINVAL, "Q3: missing column");
-
-	int32_t cutoff = p->desc.cutoff_date;
-	uint8_t segcode = p->desc.mktsegment;
-	unsigned long long *ctr =
-		(unsigned long long *) p->sget("ctr", 8);
-
-	if (!ctr)
-		return fail(GG_ENOMEM, "scratch");
-
-	/* 1. customer build side (nodeHash.c:450 sizing / :905 insert).
-	 * Dense custkeys (max <= 8x rows) collapse to a 1-bit-per-key
-	 * membership bitmap (SF100: 15M keys = 1.9 MB — resident in
-	 * every XCD's L2, unlike a 15 MB byte array); hash set fallback
-	 * for sparse keys. */
+	/* customer build side: membership bitmap or hash set */
 	DeviceHashTable cust{};
 	unsigned long long *cust_bits = nullptr;
 	int64_t cust_dlen = 0;
-	{
-		unsigned long long maxk = 0;
 
-		GG_TRY(cached_max_i64(e, p, c_ck, cu->nrows, ctr, &maxk));
-		if (cu->nrows > 0 && maxk > 0 &&
-		    maxk <= (unsigned long long) (8 * cu->nrows + 16))
-			cust_dlen = (int64_t) maxk + 1;
-	}
-	/* record which build-side layout ran (nodeHash.c:450 sizing
-	 * decision analog) so EXPLAIN-style stats show the taken path */
-	p->stat(cust_dlen ? "path_cust_bitmap" : "path_cust_hash").launches++;
-	{
-		Timed tm(e.stream);
-
-		if (cust_dlen)
-		{
-			size_t words = (size_t) (cust_dlen / 64 + 2);
-
-			cust_bits = (unsigned long long *)
-				p->sget("cust.bits", words * 8);
-			if (!cust_bits)
-				return fail(GG_ENOMEM, "cust bits");
-			GG_HIP(hipMemsetAsync(cust_bits, 0, words * 8,
-					      e.stream));
-			GG_HIP(launch_cust_dense_fill_seg(e.stream, c_ck,
-							  c_ms, cu->nrows,
-							  segcode, cust_bits,
-							  cust_dlen));
-		}
-		else
-		{
-			if (!p->cust_slots)
-			{
-				unsigned long long nfil = 0;
-
-				GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-				GG_HIP(launch_count_filter_u8(e.stream, c_ms,
-							      segcode,
-							      cu->nrows, ctr));
-				GG_HIP(hipStreamSynchronize(e.stream));
-				GG_TRY(read_counter(ctr, &nfil));
-				p->cust_slots = next_pow2(2 * (nfil + 1));
-			}
-			cust.nslots = p->cust_slots;
-			cust.bloom_words = cust.nslots / 8 < 1024
-				? 1024 : cust.nslots / 8;
-			cust.keys = (unsigned long long *)
-				p->sget("cust.keys", cust.nslots * 8);
-			cust.bloom = (unsigned long long *)
-				p->sget("cust.bloom", cust.bloom_words * 8);
-			if (!cust.keys || !cust.bloom)
-				return fail(GG_ENOMEM, "cust table");
-			GG_HIP(hipMemsetAsync(cust.keys, 0, cust.nslots * 8,
-					      e.stream));
-			GG_HIP(hipMemsetAsync(cust.bloom, 0,
-					      cust.bloom_words * 8, e.stream));
-			GG_HIP(launch_build_set(e.stream, c_ck, c_ms, segcode,
-						cu->nrows, cust));
-		}
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("build_customer");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += cu->nrows;
-		st.hbm_bytes += cu->nrows * 9;
-	}
-
-	/* 2. orders side.  Dense o_orderkey (the common case: TPC-H PK)
-	 * collapses the orders hash table to direct-map pay/rev arrays
-	 * (q3_dense.hip); hash table fallback otherwise. */
+	/* orders side: direct-map arrays or hash table */
 	DeviceHashTable ord{};
 	unsigned long long *ordd_pr = nullptr;	/* interleaved (rev, pay) */
 	unsigned long long *ordd_bloom = nullptr;
@@ -1835,614 +1778,546 @@ static gg_status exec_q3(Pipeline *p, void *arena, size_t bytes,
 	int64_t ord_dlen = 0;
 	unsigned long long nmatch = 0;
 
-	{
-		unsigned long long maxk = 0;
-
-		GG_TRY(cached_max_i64(e, p, o_ok, od->nrows, ctr, &maxk));
-		if (od->nrows > 0 && maxk > 0 &&
-		    maxk <= (unsigned long long) (8 * od->nrows + 16))
-			ord_dlen = (int64_t) maxk + 1;
-	}
-	p->stat(ord_dlen ? "path_orders_dense" : "path_orders_hash").launches++;
-	if (ord_dlen)
-	{
-		/* exact membership bitmap over dense keys */
-		ordd_bwords = (uint64_t) (ord_dlen / 64 + 2);
-		/* (rev, pay) interleave as 16-B pairs: the top-k's cold
-		 * random gathers then touch ONE cache line per survivor */
-		ordd_pr = (unsigned long long *)
-			p->sget("ordd.pr", (size_t) ord_dlen * 16);
-		ordd_bloom = (unsigned long long *)
-			p->sget("ordd.bloom", ordd_bwords * 8);
-		if (!ordd_pr || !ordd_bloom)
-			return fail(GG_ENOMEM, "ord dense");
-		/* pay slots need NO init: they are read only behind the
-		 * exact membership bitmap, which is rebuilt every pass,
-		 * so any read slot was stored this pass.  rev slots are
-		 * fully zeroed only on first use / after a fallback pass;
-		 * the fused top-k otherwise zeroes exactly the entries
-		 * the probe touched (clear over the survivor list). */
-		if (!p->q3_rev_inited || p->q3_rev_dirty)
-		{
-			GG_HIP(hipMemsetAsync(ordd_pr, 0,
-					      (size_t) ord_dlen * 16,
-					      e.stream));
-			p->q3_rev_inited = true;
-		}
-		p->q3_rev_dirty = true;	/* until the sparse clear runs */
-		GG_HIP(hipMemsetAsync(ordd_bloom, 0, ordd_bwords * 8,
-				      e.stream));
-	}
-
-	if (!exch)
-	{
-		Timed tm(e.stream);
-
-		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-		if (ord_dlen)
-		{
-			GG_HIP(launch_dn_build_orders(
-				e.stream, o_ok, o_ck, o_dt, o_pr, od->nrows,
-				cutoff, cust, cust_bits, cust_dlen, ordd_pr,
-				ord_dlen, ordd_bloom, ordd_bwords, ctr));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(read_counter(ctr, &nmatch));
-		}
-		else
-		{
-			if (!p->ord_slots)
-			{
-				GG_HIP(launch_count_orders_match(
-					e.stream, o_ck, o_dt, od->nrows,
-					cutoff, cust, cust_bits, cust_dlen,
-					ctr));
-				GG_HIP(hipStreamSynchronize(e.stream));
-				GG_TRY(read_counter(ctr, &nmatch));
-				p->ord_slots = next_pow2(2 * (nmatch + 1));
-				GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-			}
-			ord.nslots = p->ord_slots;
-			ord.bloom_words = ord.nslots / 8 < 1024
-				? 1024 : ord.nslots / 8;
-			ord.keys = (unsigned long long *)
-				p->sget("ord.keys", ord.nslots * 8);
-			ord.payload = (unsigned long long *)
-				p->sget("ord.payload", ord.nslots * 8);
-			ord.rev = (unsigned long long *)
-				p->sget("ord.rev", ord.nslots * 8);
-			ord.bloom = (unsigned long long *)
-				p->sget("ord.bloom", ord.bloom_words * 8);
-			if (!ord.keys || !ord.payload || !ord.rev || !ord.bloom)
-				return fail(GG_ENOMEM, "ord table");
-			GG_HIP(hipMemsetAsync(ord.keys, 0, ord.nslots * 8,
-					      e.stream));
-			GG_HIP(hipMemsetAsync(ord.rev, 0, ord.nslots * 8,
-					      e.stream));
-			GG_HIP(hipMemsetAsync(ord.bloom, 0,
-					      ord.bloom_words * 8, e.stream));
-			GG_HIP(launch_build_orders(e.stream, o_ok, o_ck, o_dt,
-						   o_pr, od->nrows, cutoff,
-						   cust, cust_bits, cust_dlen,
-						   ord, ctr));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(read_counter(ctr, &nmatch));
-		}
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("build_orders");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += od->nrows;
-		st.rows_out += (int64_t) nmatch;
-		st.hbm_bytes += od->nrows * 24;
-	}
-	else
-	{
-		/* Motion redistribute legs:
-		 * leg 1: filtered orders → owner of o_custkey;
-		 * leg 2: customer-joined orders → owner of o_orderkey. */
-		if (!comm_ready())
-			return fail(GG_ESTATE,
-				    "exchange path requires gg_engine_comm_init");
-		Timed tm(e.stream);
-
-		int64_t *f_ck = (int64_t *) p->sget("f_ck", (od->nrows + 1) * 8);
-		int64_t *f_ok = (int64_t *) p->sget("f_ok", (od->nrows + 1) * 8);
-		int64_t *f_pay = (int64_t *) p->sget("f_pay", (od->nrows + 1) * 8);
-		unsigned long long *dcnt =
-			(unsigned long long *) p->sget("dcnt", (size_t) nseg * 8);
-		unsigned long long *doffs =
-			(unsigned long long *) p->sget("doffs", (size_t) nseg * 8);
-
-		if (!f_ck || !f_ok || !f_pay || !dcnt || !doffs)
-			return fail(GG_ENOMEM, "exchange scratch");
-
-		unsigned long long nfil = 0;
-
-		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-		GG_HIP(launch_orders_filter_compact(e.stream, o_ok, o_ck, o_dt,
-						    o_pr, od->nrows,
-						    INT32_MIN, cutoff,
-						    f_ck, f_ok, f_pay, ctr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_TRY(read_counter(ctr, &nfil));
-
-		/* partition by custkey (doSendTuple routing,
-		 * nodeMotion.c:1600–1636, bit-exact cdbhash) */
-		std::vector<unsigned long long> cnts(nseg), offs(nseg + 1, 0);
-
-		GG_HIP(hipMemsetAsync(dcnt, 0, (size_t) nseg * 8, e.stream));
-		GG_HIP(launch_part_count(e.stream, f_ck, (int64_t) nfil, nseg,
-					 dcnt));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_HIP(hipMemcpy(cnts.data(), dcnt, (size_t) nseg * 8,
-				 hipMemcpyDeviceToHost));
-		for (int i = 0; i < nseg; i++)
-			offs[i + 1] = offs[i] + cnts[i];
-
-		int64_t *s_ck = (int64_t *) p->sget("s_ck", (nfil + 1) * 8);
-		int64_t *s_ok = (int64_t *) p->sget("s_ok", (nfil + 1) * 8);
-		int64_t *s_pay = (int64_t *) p->sget("s_pay", (nfil + 1) * 8);
-
-		if (!s_ck || !s_ok || !s_pay)
-			return fail(GG_ENOMEM, "send scratch");
-		GG_HIP(hipMemcpy(doffs, offs.data(), (size_t) nseg * 8,
-				 hipMemcpyHostToDevice));
-		GG_HIP(launch_part_scatter3(e.stream, f_ck, (int64_t) nfil,
-					    nseg, f_ck, f_ok, f_pay, doffs,
-					    s_ck, s_ok, s_pay));
-		GG_HIP(hipStreamSynchronize(e.stream));
-
-		/* exchange the count vector, derive receive layout */
-		std::vector<unsigned long long> allcnt((size_t) nseg * nseg);
-		{
-			unsigned long long *g = (unsigned long long *)
-				p->sget("cntg", (size_t) (nseg + nseg * nseg) * 8);
-
-			if (!g)
-				return fail(GG_ENOMEM, "cnt allgather");
-			GG_HIP(hipMemcpy(g, cnts.data(), (size_t) nseg * 8,
-					 hipMemcpyHostToDevice));
-			GG_TRY(comm_allgather_u64(g, g + nseg, nseg));
-			GG_HIP(hipMemcpy(allcnt.data(), g + nseg,
-					 allcnt.size() * 8,
-					 hipMemcpyDeviceToHost));
-		}
-		std::vector<unsigned long long> rcnts(nseg), roffs(nseg + 1, 0);
-
-		for (int s2 = 0; s2 < nseg; s2++)
-			rcnts[s2] = allcnt[(size_t) s2 * nseg + me];
-		for (int i = 0; i < nseg; i++)
-			roffs[i + 1] = roffs[i] + rcnts[i];
-		uint64_t rtotal = roffs[nseg];
-
-		int64_t *r_ck = (int64_t *) p->sget("r_ck", (rtotal + 1) * 8);
-		int64_t *r_ok = (int64_t *) p->sget("r_ok", (rtotal + 1) * 8);
-		int64_t *r_pay = (int64_t *) p->sget("r_pay", (rtotal + 1) * 8);
-
-		if (!r_ck || !r_ok || !r_pay)
-			return fail(GG_ENOMEM, "recv scratch");
-		GG_TRY(comm_alltoallv_i64(s_ck, offs.data(), cnts.data(),
-					  r_ck, roffs.data(), rcnts.data()));
-		GG_TRY(comm_alltoallv_i64(s_ok, offs.data(), cnts.data(),
-					  r_ok, roffs.data(), rcnts.data()));
-		GG_TRY(comm_alltoallv_i64(s_pay, offs.data(), cnts.data(),
-					  r_pay, roffs.data(), rcnts.data()));
-
-		/* probe local customer set → matched (okey, pay) */
-		unsigned long long nm = 0;
-		int64_t *m_ok = (int64_t *) p->sget("m_ok", (rtotal + 1) * 8);
-		int64_t *m_pay = (int64_t *) p->sget("m_pay", (rtotal + 1) * 8);
-
-		if (!m_ok || !m_pay)
-			return fail(GG_ENOMEM, "match scratch");
-		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-		GG_HIP(launch_probe_cust_compact(e.stream, r_ck, r_ok, r_pay,
-						 (int64_t) rtotal, cust,
-						 cust_bits, cust_dlen, m_ok,
-						 m_pay, ctr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_TRY(read_counter(ctr, &nm));
-
-		/* leg 2: matched orders → owner of o_orderkey */
-		std::vector<unsigned long long> cnts2(nseg), offs2(nseg + 1, 0);
-
-		GG_HIP(hipMemsetAsync(dcnt, 0, (size_t) nseg * 8, e.stream));
-		GG_HIP(launch_part_count(e.stream, m_ok, (int64_t) nm, nseg,
-					 dcnt));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_HIP(hipMemcpy(cnts2.data(), dcnt, (size_t) nseg * 8,
-				 hipMemcpyDeviceToHost));
-		for (int i = 0; i < nseg; i++)
-			offs2[i + 1] = offs2[i] + cnts2[i];
-
-		int64_t *s2_ok = (int64_t *) p->sget("s2_ok", (nm + 1) * 8);
-		int64_t *s2_pay = (int64_t *) p->sget("s2_pay", (nm + 1) * 8);
-
-		if (!s2_ok || !s2_pay)
-			return fail(GG_ENOMEM, "send2 scratch");
-		GG_HIP(hipMemcpy(doffs, offs2.data(), (size_t) nseg * 8,
-				 hipMemcpyHostToDevice));
-		GG_HIP(launch_part_scatter3(e.stream, m_ok, (int64_t) nm, nseg,
-					    m_ok, m_pay, nullptr, doffs,
-					    s2_ok, s2_pay, nullptr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-
-		std::vector<unsigned long long> allcnt2((size_t) nseg * nseg);
-		{
-			unsigned long long *g = (unsigned long long *)
-				p->sget("cntg", (size_t) (nseg + nseg * nseg) * 8);
-
-			GG_HIP(hipMemcpy(g, cnts2.data(), (size_t) nseg * 8,
-					 hipMemcpyHostToDevice));
-			GG_TRY(comm_allgather_u64(g, g + nseg, nseg));
-			GG_HIP(hipMemcpy(allcnt2.data(), g + nseg,
-					 allcnt2.size() * 8,
-					 hipMemcpyDeviceToHost));
-		}
-		std::vector<unsigned long long> rcnts2(nseg), roffs2(nseg + 1, 0);
-
-		for (int s2 = 0; s2 < nseg; s2++)
-			rcnts2[s2] = allcnt2[(size_t) s2 * nseg + me];
-		for (int i = 0; i < nseg; i++)
-			roffs2[i + 1] = roffs2[i] + rcnts2[i];
-		uint64_t rtotal2 = roffs2[nseg];
-
-		int64_t *r2_ok = (int64_t *) p->sget("r2_ok", (rtotal2 + 1) * 8);
-		int64_t *r2_pay = (int64_t *) p->sget("r2_pay", (rtotal2 + 1) * 8);
-
-		if (!r2_ok || !r2_pay)
-			return fail(GG_ENOMEM, "recv2 scratch");
-		GG_TRY(comm_alltoallv_i64(s2_ok, offs2.data(), cnts2.data(),
-					  r2_ok, roffs2.data(), rcnts2.data()));
-		GG_TRY(comm_alltoallv_i64(s2_pay, offs2.data(), cnts2.data(),
-					  r2_pay, roffs2.data(),
-					  rcnts2.data()));
-
-		nmatch = rtotal2;
-		if (ord_dlen)
-		{
-			GG_HIP(launch_dn_insert_orders(e.stream, r2_ok, r2_pay,
-						       (int64_t) rtotal2,
-						       ordd_pr, ord_dlen,
-						       ordd_bloom,
-						       ordd_bwords));
-			GG_HIP(hipStreamSynchronize(e.stream));
-		}
-		else
-		{
-			if (!p->ord_slots)
-				p->ord_slots = next_pow2(2 * (rtotal2 + 1));
-			ord.nslots = p->ord_slots;
-			ord.bloom_words = ord.nslots / 8 < 1024
-				? 1024 : ord.nslots / 8;
-			ord.keys = (unsigned long long *)
-				p->sget("ord.keys", ord.nslots * 8);
-			ord.payload = (unsigned long long *)
-				p->sget("ord.payload", ord.nslots * 8);
-			ord.rev = (unsigned long long *)
-				p->sget("ord.rev", ord.nslots * 8);
-			ord.bloom = (unsigned long long *)
-				p->sget("ord.bloom", ord.bloom_words * 8);
-			if (!ord.keys || !ord.payload || !ord.rev || !ord.bloom)
-				return fail(GG_ENOMEM, "ord table");
-			GG_HIP(hipMemsetAsync(ord.keys, 0, ord.nslots * 8,
-					      e.stream));
-			GG_HIP(hipMemsetAsync(ord.rev, 0, ord.nslots * 8,
-					      e.stream));
-			GG_HIP(hipMemsetAsync(ord.bloom, 0,
-					      ord.bloom_words * 8, e.stream));
-			GG_HIP(launch_insert_orders(e.stream, r2_ok, r2_pay,
-						    (int64_t) rtotal2, ord));
-			GG_HIP(hipStreamSynchronize(e.stream));
-		}
-
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("orders_exchange");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += od->nrows;
-		st.rows_out += (int64_t) nmatch;
-	}
-
-	/* 3. lineitem probe + group aggregation (probe fused with the
-	 * group-by transition; group slot ≡ matched-order slot).  The
-	 * dense probe also appends each group's index ONCE (0→nonzero
-	 * rev transition) into a per-block survivor region — LDS
-	 * counter, no contended global atomic — so the top-k never
-	 * sweeps the dense array. */
+	/* lineitem probe: join rows and the dense path's survivor list */
 	unsigned long long njoin = 0, sovf = 0;
 	unsigned long long *dsurv = nullptr, *dscnt = nullptr,
 		*dsovf = nullptr;
 	uint64_t region = 0;
 	int pgrid = 0;
 
-	if (ord_dlen)
-	{
-		pgrid = dn_probe_grid(li->nrows);
-		region = 2 * ((uint64_t) nmatch / (uint64_t) pgrid) + 256;
-		dsurv = (unsigned long long *)
-			p->sget("surv", (size_t) pgrid * region * 8);
-		dscnt = (unsigned long long *)
-			p->sget("surv.cnts", (size_t) pgrid * 8);
-		dsovf = (unsigned long long *) p->sget("surv.ovf", 8);
-		if (!dsurv || !dscnt || !dsovf)
-			return fail(GG_ENOMEM, "survivor scratch");
-		GG_HIP(hipMemsetAsync(dsovf, 0, 8, e.stream));
-	}
-	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-	{
-		Timed tm(e.stream);
-
-		if (ord_dlen)
-			GG_HIP(launch_dn_probe_lineitem(
-				e.stream, l_ok, l_sd, l_pc, l_dc, li->nrows,
-				cutoff, ordd_pr, ord_dlen,
-				ordd_bloom, ordd_bwords, ctr, dsurv, region,
-				dscnt, dsovf, pgrid));
-		else
-			GG_HIP(launch_probe_lineitem(e.stream, l_ok, l_sd,
-						     l_pc, l_dc, li->nrows,
-						     cutoff, ord, ctr));
-		double ms = tm.stop();
-		GG_TRY(read_counter(ctr, &njoin));
-		if (ord_dlen)
-			GG_TRY(read_counter(dsovf, &sovf));
-		KernelStatAcc &st = p->stat("probe_lineitem");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += li->nrows;
-		st.rows_out += (int64_t) njoin;
-		st.hbm_bytes += li->nrows * 28;	/* SURVEY §8(d) */
-	}
-
-	/* 4. top-k select.  Dense path: stats+hist, threshold, collect
-	 * and sparse clear all walk the ~ngroups survivor list the probe
-	 * recorded — no sweep of the GB-sized dense array, no host round
-	 * trip between kernels.  Hash-table path: the original
-	 * stats→hist→collect sweeps. */
+	/* top-k: ngroups, rev lo, rev hi, checksum, max rev; candidates */
+	unsigned long long *stats5 = nullptr;
 	unsigned long long hstats[5] = {0, 0, 0, 0, 0};
-	unsigned long long *stats5 =
-		(unsigned long long *) p->sget("stats5", 5 * 8);
+	std::vector<gg_q3_result_row> cand;
+};
 
-	if (!stats5)
-		return fail(GG_ENOMEM, "stats scratch");
+/* 1. customer build side (nodeHash.c:450 sizing / :905 insert).
+ * Dense custkeys (max <= 8x rows) collapse to a 1-bit-per-key
+ * membership bitmap (SF100: 15M keys = 1.9 MB — resident in
+ * every XCD's L2, unlike a 15 MB byte array); hash set fallback
+ * for sparse keys. */
+static gg_status q3_build_customer(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.cu->nrows;
+
+	GG_TRY(dense_key_len(e, p, S.c_ck, nrows, S.ctr, &S.cust_dlen));
+	/* record which build-side layout ran (nodeHash.c:450 sizing
+	 * decision analog) so EXPLAIN-style stats show the taken path */
+	p->stat(S.cust_dlen ? "path_cust_bitmap" : "path_cust_hash").launches++;
+
+	Timed tm(e.stream);
+
+	if (S.cust_dlen)
 	{
-		Timed tm(e.stream);
-		std::vector<gg_q3_result_row> cand;
-		bool need_old = !ord_dlen || sovf != 0;
+		size_t words = (size_t) (S.cust_dlen / 64 + 2);
 
-		if (!need_old)
+		S.cust_bits = (unsigned long long *)
+			p->sget("cust.bits", words * 8);
+		if (!S.cust_bits)
+			return fail(GG_ENOMEM, "cust bits");
+		GG_HIP(hipMemsetAsync(S.cust_bits, 0, words * 8, e.stream));
+		GG_HIP(launch_cust_dense_fill_seg(e.stream, S.c_ck, S.c_ms,
+						  nrows, S.segcode,
+						  S.cust_bits, S.cust_dlen));
+	}
+	else
+	{
+		if (!p->cust_slots)
 		{
-			uint64_t cap = 4 * (uint64_t) k + 65536;
-			unsigned int *dhist =
-				(unsigned int *) p->sget("hist", 65536 * 4);
-			unsigned long long *dthr =
-				(unsigned long long *) p->sget("thr", 8);
-			gg_q3_result_row *dout = (gg_q3_result_row *)
-				p->sget("cand", cap * sizeof(gg_q3_result_row));
-			unsigned long long ncand = 0;
+			unsigned long long nfil = 0;
 
-			if (!dhist || !dthr || !dout)
-				return fail(GG_ENOMEM, "topk scratch");
-			GG_HIP(hipMemsetAsync(stats5, 0, 5 * 8, e.stream));
-			GG_HIP(hipMemsetAsync(dhist, 0, 65536 * 4, e.stream));
-			GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-			GG_HIP(launch_dn_q3_stats_surv(e.stream, dsurv,
-						       dscnt, region, pgrid,
-						       ordd_pr,
-						       stats5, dhist));
-			GG_HIP(launch_dn_q3_threshold2(e.stream, dhist, k,
-						       dthr));
-			GG_HIP(launch_dn_q3_collect_surv(
-				e.stream, dsurv, dscnt, region, pgrid,
-				ordd_pr, dthr, dout, ctr, cap));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_HIP(hipMemcpy(hstats, stats5, 40,
-					 hipMemcpyDeviceToHost));
-			GG_TRY(read_counter(ctr, &ncand));
-			if (ncand > cap)
-			{
-				/* tie-heavy threshold bin: retry collect
-				 * alone with an exact-size buffer */
-				cap = hstats[0] + 1;
-				dout = (gg_q3_result_row *) p->sget(
-					"cand",
-					cap * sizeof(gg_q3_result_row));
-				if (!dout)
-					return fail(GG_ENOMEM, "topk retry");
-				GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-				GG_HIP(launch_dn_q3_collect_surv(
-					e.stream, dsurv, dscnt, region,
-					pgrid, ordd_pr, dthr,
-					dout, ctr, cap));
-				GG_HIP(hipStreamSynchronize(e.stream));
-				GG_TRY(read_counter(ctr, &ncand));
-				if (ncand > cap)
-					return fail(GG_EINVAL,
-						    "top-k overflow (%llu)",
-						    ncand);
-			}
-			if (ncand)
-			{
-				cand.resize(ncand);
-				GG_HIP(hipMemcpy(cand.data(), dout,
-						 ncand * sizeof(gg_q3_result_row),
-						 hipMemcpyDeviceToHost));
-			}
-			/* zero only the touched rev[] entries so the next
-			 * execute skips the dense memset (runs async;
-			 * later work queues behind it on the stream) */
-			GG_HIP(launch_dn_q3_clear_surv(e.stream, dsurv,
-						       dscnt, region, pgrid,
-						       ordd_pr));
-			p->q3_rev_dirty = false;
+			GG_TRY(run_counted(e.stream, S.ctr, &nfil, [&] {
+				return launch_count_filter_u8(
+					e.stream, S.c_ms, S.segcode, nrows,
+					S.ctr);
+			}));
+			p->cust_slots = next_pow2(2 * (nfil + 1));
 		}
+		GG_TRY(hash_table_alloc(p, "cust", p->cust_slots, HT_BLOOM,
+					&S.cust));
+		GG_HIP(launch_build_set(e.stream, S.c_ck, S.c_ms, S.segcode,
+					nrows, S.cust));
+	}
+	p->stat("build_customer").add(tm.stop(), nrows, 0, nrows * 9);
+	return GG_OK;
+}
 
-		if (need_old)
+/* 2. orders side.  Dense o_orderkey (the common case: TPC-H PK)
+ * collapses the orders hash table to direct-map pay/rev arrays
+ * (q3_dense.hip); hash table fallback otherwise.  This step picks the
+ * layout and readies the dense arrays; the build (local) or the exchange
+ * fills them. */
+static gg_status q3_orders_layout(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+
+	GG_TRY(dense_key_len(e, p, S.o_ok, S.od->nrows, S.ctr, &S.ord_dlen));
+	p->stat(S.ord_dlen ? "path_orders_dense" : "path_orders_hash").launches++;
+	if (!S.ord_dlen)
+		return GG_OK;
+	/* exact membership bitmap over dense keys */
+	S.ordd_bwords = (uint64_t) (S.ord_dlen / 64 + 2);
+	/* (rev, pay) interleave as 16-B pairs: the top-k's cold
+	 * random gathers then touch ONE cache line per survivor */
+	S.ordd_pr = (unsigned long long *)
+		p->sget("ordd.pr", (size_t) S.ord_dlen * 16);
+	S.ordd_bloom = (unsigned long long *)
+		p->sget("ordd.bloom", S.ordd_bwords * 8);
+	if (!S.ordd_pr || !S.ordd_bloom)
+		return fail(GG_ENOMEM, "ord dense");
+	/* pay slots need NO init: they are read only behind the
+	 * exact membership bitmap, which is rebuilt every pass,
+	 * so any read slot was stored this pass.  rev slots are
+	 * fully zeroed only on first use / after a fallback pass;
+	 * the fused top-k otherwise zeroes exactly the entries
+	 * the probe touched (clear over the survivor list). */
+	if (!p->q3_rev_inited || p->q3_rev_dirty)
+	{
+		GG_HIP(hipMemsetAsync(S.ordd_pr, 0, (size_t) S.ord_dlen * 16,
+				      e.stream));
+		p->q3_rev_inited = true;
+	}
+	p->q3_rev_dirty = true;	/* until the sparse clear runs */
+	GG_HIP(hipMemsetAsync(S.ordd_bloom, 0, S.ordd_bwords * 8, e.stream));
+	return GG_OK;
+}
+
+/* 2a. orders build, single segment: filter + customer probe + insert fused */
+static gg_status q3_build_orders_local(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.od->nrows;
+	Timed tm(e.stream);
+
+	if (S.ord_dlen)
+		GG_TRY(run_counted(e.stream, S.ctr, &S.nmatch, [&] {
+			return launch_dn_build_orders(
+				e.stream, S.o_ok, S.o_ck, S.o_dt, S.o_pr,
+				nrows, S.cutoff, S.cust, S.cust_bits,
+				S.cust_dlen, S.ordd_pr, S.ord_dlen,
+				S.ordd_bloom, S.ordd_bwords, S.ctr);
+		}));
+	else
+	{
+		if (!p->ord_slots)
 		{
-			GG_HIP(hipMemsetAsync(stats5, 0, 5 * 8, e.stream));
-			if (ord_dlen)
-				GG_HIP(launch_dn_q3_stats(e.stream, ordd_pr,
-							  ord_dlen,
-							  stats5));
-			else
-				GG_HIP(launch_q3_stats(e.stream, ord, stats5));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_HIP(hipMemcpy(hstats, stats5, 40,
-					 hipMemcpyDeviceToHost));
+			GG_TRY(run_counted(e.stream, S.ctr, &S.nmatch, [&] {
+				return launch_count_orders_match(
+					e.stream, S.o_ck, S.o_dt, nrows,
+					S.cutoff, S.cust, S.cust_bits,
+					S.cust_dlen, S.ctr);
+			}));
+			p->ord_slots = next_pow2(2 * (S.nmatch + 1));
+		}
+		GG_TRY(hash_table_alloc(p, "ord", p->ord_slots,
+					HT_PAYLOAD | HT_REV | HT_BLOOM,
+					&S.ord));
+		GG_TRY(run_counted(e.stream, S.ctr, &S.nmatch, [&] {
+			return launch_build_orders(
+				e.stream, S.o_ok, S.o_ck, S.o_dt, S.o_pr,
+				nrows, S.cutoff, S.cust, S.cust_bits,
+				S.cust_dlen, S.ord, S.ctr);
+		}));
+	}
+	p->stat("build_orders").add(tm.stop(), nrows, (int64_t) S.nmatch,
+				    nrows * 24);
+	return GG_OK;
+}
 
-			unsigned long long maxrev = hstats[4];
+/* 2b. orders build across segments: the Motion redistribute legs
+ * (SURVEY §8(e)):
+ * leg 1: filtered orders → owner of o_custkey;
+ * leg 2: customer-joined orders → owner of o_orderkey. */
+static gg_status q3_orders_exchange(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.od->nrows;
 
-			cand.clear();
-			if (maxrev > 0)
+	if (!comm_ready())
+		return fail(GG_ESTATE,
+			    "exchange path requires gg_engine_comm_init");
+	Timed tm(e.stream);
+	int64_t *f_ck = (int64_t *) p->sget("f_ck", (nrows + 1) * 8);
+	int64_t *f_ok = (int64_t *) p->sget("f_ok", (nrows + 1) * 8);
+	int64_t *f_pay = (int64_t *) p->sget("f_pay", (nrows + 1) * 8);
+	unsigned long long nfil = 0, nm = 0;
+
+	if (!f_ck || !f_ok || !f_pay)
+		return fail(GG_ENOMEM, "exchange scratch");
+	GG_TRY(run_counted(e.stream, S.ctr, &nfil, [&] {
+		return launch_orders_filter_compact(
+			e.stream, S.o_ok, S.o_ck, S.o_dt, S.o_pr, nrows,
+			INT32_MIN, S.cutoff, f_ck, f_ok, f_pay, S.ctr);
+	}));
+
+	/* leg 1, partitioned by custkey */
+	const int64_t *in1[3] = {f_ck, f_ok, f_pay};
+	int64_t *r1[3];
+	uint64_t rtotal = 0;
+
+	GG_TRY(motion_redistribute(p, f_ck, in1, (int64_t) nfil, "leg1", r1,
+				   &rtotal));
+
+	/* probe local customer set → matched (okey, pay) */
+	int64_t *m_ok = (int64_t *) p->sget("m_ok", (rtotal + 1) * 8);
+	int64_t *m_pay = (int64_t *) p->sget("m_pay", (rtotal + 1) * 8);
+
+	if (!m_ok || !m_pay)
+		return fail(GG_ENOMEM, "match scratch");
+	GG_TRY(run_counted(e.stream, S.ctr, &nm, [&] {
+		return launch_probe_cust_compact(
+			e.stream, r1[0], r1[1], r1[2], (int64_t) rtotal,
+			S.cust, S.cust_bits, S.cust_dlen, m_ok, m_pay, S.ctr);
+	}));
+
+	/* leg 2: matched orders → owner of o_orderkey */
+	const int64_t *in2[3] = {m_ok, m_pay, nullptr};
+	int64_t *r2[3];
+	uint64_t rtotal2 = 0;
+
+	GG_TRY(motion_redistribute(p, m_ok, in2, (int64_t) nm, "leg2", r2,
+				   &rtotal2));
+	S.nmatch = rtotal2;
+	if (S.ord_dlen)
+		GG_HIP(launch_dn_insert_orders(e.stream, r2[0], r2[1],
+					       (int64_t) rtotal2, S.ordd_pr,
+					       S.ord_dlen, S.ordd_bloom,
+					       S.ordd_bwords));
+	else
+	{
+		if (!p->ord_slots)
+			p->ord_slots = next_pow2(2 * (rtotal2 + 1));
+		GG_TRY(hash_table_alloc(p, "ord", p->ord_slots,
+					HT_PAYLOAD | HT_REV | HT_BLOOM,
+					&S.ord));
+		GG_HIP(launch_insert_orders(e.stream, r2[0], r2[1],
+					    (int64_t) rtotal2, S.ord));
+	}
+	GG_HIP(hipStreamSynchronize(e.stream));
+	p->stat("orders_exchange").add(tm.stop(), nrows, (int64_t) S.nmatch);
+	return GG_OK;
+}
+
+/* 3. lineitem probe + group aggregation (probe fused with the
+ * group-by transition; group slot ≡ matched-order slot).  The
+ * dense probe also appends each group's index ONCE (0→nonzero
+ * rev transition) into a per-block survivor region — LDS
+ * counter, no contended global atomic — so the top-k never
+ * sweeps the dense array. */
+static gg_status q3_probe_lineitem(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.li->nrows;
+
+	if (S.ord_dlen)
+	{
+		S.pgrid = dn_probe_grid(nrows);
+		S.region = 2 * ((uint64_t) S.nmatch / (uint64_t) S.pgrid) + 256;
+		S.dsurv = (unsigned long long *)
+			p->sget("surv", (size_t) S.pgrid * S.region * 8);
+		S.dscnt = (unsigned long long *)
+			p->sget("surv.cnts", (size_t) S.pgrid * 8);
+		S.dsovf = (unsigned long long *) p->sget("surv.ovf", 8);
+		if (!S.dsurv || !S.dscnt || !S.dsovf)
+			return fail(GG_ENOMEM, "survivor scratch");
+		GG_HIP(hipMemsetAsync(S.dsovf, 0, 8, e.stream));
+	}
+	GG_HIP(hipMemsetAsync(S.ctr, 0, 8, e.stream));
+
+	Timed tm(e.stream);
+
+	if (S.ord_dlen)
+		GG_HIP(launch_dn_probe_lineitem(
+			e.stream, S.l_ok, S.l_sd, S.l_pc, S.l_dc, nrows,
+			S.cutoff, S.ordd_pr, S.ord_dlen, S.ordd_bloom,
+			S.ordd_bwords, S.ctr, S.dsurv, S.region, S.dscnt,
+			S.dsovf, S.pgrid));
+	else
+		GG_HIP(launch_probe_lineitem(e.stream, S.l_ok, S.l_sd, S.l_pc,
+					     S.l_dc, nrows, S.cutoff, S.ord,
+					     S.ctr));
+	double ms = tm.stop();
+
+	GG_TRY(read_counter(S.ctr, &S.njoin));
+	if (S.ord_dlen)
+		GG_TRY(read_counter(S.dsovf, &S.sovf));
+	/* 28 B/row */
+	p->stat("probe_lineitem").add(ms, nrows, (int64_t) S.njoin,
+				      nrows * 28);
+	return GG_OK;
+}
+
+/* copy ncand collected candidates off the device */
+static gg_status q3_fetch_cand(Q3State &S, const gg_q3_result_row *dout,
+			       unsigned long long ncand)
+{
+	S.cand.resize(ncand);
+	if (ncand)
+		GG_HIP(hipMemcpy(S.cand.data(), dout,
+				 ncand * sizeof(gg_q3_result_row),
+				 hipMemcpyDeviceToHost));
+	return GG_OK;
+}
+
+/* 4a. top-k candidates, dense path: stats+hist, threshold, collect
+ * and sparse clear all walk the ~ngroups survivor list the probe
+ * recorded — no sweep of the GB-sized dense array, no host round
+ * trip between kernels. */
+static gg_status q3_topk_survivors(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	uint64_t cap = 4 * (uint64_t) S.k + 65536;
+	unsigned int *dhist = (unsigned int *) p->sget("hist", 65536 * 4);
+	unsigned long long *dthr = (unsigned long long *) p->sget("thr", 8);
+	gg_q3_result_row *dout = (gg_q3_result_row *)
+		p->sget("cand", cap * sizeof(gg_q3_result_row));
+	unsigned long long ncand = 0;
+
+	if (!dhist || !dthr || !dout)
+		return fail(GG_ENOMEM, "topk scratch");
+	GG_HIP(hipMemsetAsync(S.stats5, 0, 5 * 8, e.stream));
+	GG_HIP(hipMemsetAsync(dhist, 0, 65536 * 4, e.stream));
+	GG_HIP(hipMemsetAsync(S.ctr, 0, 8, e.stream));
+	GG_HIP(launch_dn_q3_stats_surv(e.stream, S.dsurv, S.dscnt, S.region,
+				       S.pgrid, S.ordd_pr, S.stats5, dhist));
+	GG_HIP(launch_dn_q3_threshold2(e.stream, dhist, S.k, dthr));
+	GG_HIP(launch_dn_q3_collect_surv(e.stream, S.dsurv, S.dscnt, S.region,
+					 S.pgrid, S.ordd_pr, dthr, dout,
+					 S.ctr, cap));
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_HIP(hipMemcpy(S.hstats, S.stats5, 40, hipMemcpyDeviceToHost));
+	GG_TRY(read_counter(S.ctr, &ncand));
+	if (ncand > cap)
+	{
+		/* tie-heavy threshold bin: retry collect
+		 * alone with an exact-size buffer */
+		cap = S.hstats[0] + 1;
+		dout = (gg_q3_result_row *)
+			p->sget("cand", cap * sizeof(gg_q3_result_row));
+		if (!dout)
+			return fail(GG_ENOMEM, "topk retry");
+		GG_TRY(run_counted(e.stream, S.ctr, &ncand, [&] {
+			return launch_dn_q3_collect_surv(
+				e.stream, S.dsurv, S.dscnt, S.region, S.pgrid,
+				S.ordd_pr, dthr, dout, S.ctr, cap);
+		}));
+		if (ncand > cap)
+			return fail(GG_EINVAL, "top-k overflow (%llu)", ncand);
+	}
+	GG_TRY(q3_fetch_cand(S, dout, ncand));
+	/* zero only the touched rev[] entries so the next
+	 * execute skips the dense memset (runs async;
+	 * later work queues behind it on the stream) */
+	GG_HIP(launch_dn_q3_clear_surv(e.stream, S.dsurv, S.dscnt, S.region,
+				       S.pgrid, S.ordd_pr));
+	p->q3_rev_dirty = false;
+	return GG_OK;
+}
+
+/* 4b. top-k candidates, hash-table path (and the dense path after a
+ * survivor-region overflow): the original stats→hist→collect sweeps */
+static gg_status q3_topk_sweep(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+
+	GG_HIP(hipMemsetAsync(S.stats5, 0, 5 * 8, e.stream));
+	if (S.ord_dlen)
+		GG_HIP(launch_dn_q3_stats(e.stream, S.ordd_pr, S.ord_dlen,
+					  S.stats5));
+	else
+		GG_HIP(launch_q3_stats(e.stream, S.ord, S.stats5));
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_HIP(hipMemcpy(S.hstats, S.stats5, 40, hipMemcpyDeviceToHost));
+	if (S.hstats[4] == 0)	/* max revenue: no group at all */
+		return GG_OK;
+
+	unsigned int *dhist = (unsigned int *) p->sget("hist", 65536 * 4);
+	unsigned long long *dthr = (unsigned long long *) p->sget("thr", 8);
+	uint64_t cap = S.hstats[0] + 1;	/* <= n_groups */
+	gg_q3_result_row *dout = (gg_q3_result_row *)
+		p->sget("cand", cap * sizeof(gg_q3_result_row));
+	unsigned long long ncand = 0;
+
+	if (!dhist || !dthr || !dout)
+		return fail(GG_ENOMEM, "topk scratch");
+	GG_HIP(hipMemsetAsync(dhist, 0, 65536 * 4, e.stream));
+	GG_HIP(hipMemsetAsync(S.ctr, 0, 8, e.stream));
+	if (S.ord_dlen)
+	{
+		GG_HIP(launch_dn_q3_hist(e.stream, S.ordd_pr, S.ord_dlen,
+					 S.stats5, dhist));
+		GG_HIP(launch_q3_threshold(e.stream, dhist, S.stats5, S.k,
+					   dthr));
+		GG_HIP(launch_dn_q3_collect(e.stream, S.ordd_pr, S.ord_dlen,
+					    dthr, dout, S.ctr, cap));
+	}
+	else
+	{
+		GG_HIP(launch_q3_hist(e.stream, S.ord, S.stats5, dhist));
+		GG_HIP(launch_q3_threshold(e.stream, dhist, S.stats5, S.k,
+					   dthr));
+		GG_HIP(launch_q3_collect(e.stream, S.ord, dthr, dout, S.ctr,
+					 cap));
+	}
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_TRY(read_counter(S.ctr, &ncand));
+	if (ncand > cap)
+		return fail(GG_EINVAL, "top-k candidate overflow (%llu)",
+			    ncand);
+	return q3_fetch_cand(S, dout, ncand);
+}
+
+/* 4. top-k select: this segment's first k groups, in result order */
+static gg_status q3_select_topk(Q3State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+
+	S.stats5 = (unsigned long long *) p->sget("stats5", 5 * 8);
+	if (!S.stats5)
+		return fail(GG_ENOMEM, "stats scratch");
+	Timed tm(e.stream);
+
+	if (S.ord_dlen && !S.sovf)
+		GG_TRY(q3_topk_survivors(S));
+	else
+		GG_TRY(q3_topk_sweep(S));
+	std::sort(S.cand.begin(), S.cand.end(), Q3TopkCmp());
+	if ((int64_t) S.cand.size() > S.k)
+		S.cand.resize(S.k);
+	/* dominant traffic: one 8 B/slot sweep of the dense rev
+	 * array (survivor finish pass is ~ngroups gathers) */
+	p->stat("q3_topk").add(tm.stop(), (int64_t) S.hstats[0],
+			       (int64_t) S.cand.size(),
+			       S.ord_dlen ? S.ord_dlen * 8
+			       : (int64_t) S.ord.nslots * 16);
+	return GG_OK;
+}
+
+/* 5. global combine (the Gather Motion to the QD: nodeMotion gather +
+ * final-stage combine), and the result into the arena */
+static gg_status q3_combine(Q3State &S, void *arena, size_t *written)
+{
+	const int nseg = engine().cfg.n_segments;
+	const int64_t k = S.k;
+	std::vector<gg_q3_result_row> &cand = S.cand;
+	u128 revsum = ((u128) S.hstats[1]) | ((u128) S.hstats[2] << 64);
+	uint64_t ngroups = S.hstats[0];
+	uint64_t checksum = S.hstats[3];
+	uint64_t njoin_g = S.njoin;
+
+	if (nseg > 1)
+	{
+		size_t per = 5 + (size_t) k * 4;
+		std::vector<unsigned long long> lbuf(per, 0), all;
+
+		lbuf[0] = ngroups;
+		lbuf[1] = (uint64_t) revsum;
+		lbuf[2] = (uint64_t) (revsum >> 64);
+		lbuf[3] = njoin_g;
+		lbuf[4] = checksum;
+		for (size_t i = 0; i < cand.size(); i++)
+			std::memcpy(&lbuf[5 + i * 4], &cand[i], 32);
+		GG_TRY(allgather_host_u64(S.p, "gatherg", lbuf.data(), per,
+					  all));
+
+		ngroups = 0;
+		revsum = 0;
+		checksum = 0;
+		njoin_g = 0;
+		cand.clear();
+		for (int r = 0; r < nseg; r++)
+		{
+			const unsigned long long *v = &all[per * (size_t) r];
+
+			ngroups += v[0];
+			revsum += ((u128) v[1]) | ((u128) v[2] << 64);
+			njoin_g += v[3];
+			checksum += v[4];
+			for (int64_t i = 0; i < k; i++)
 			{
-				unsigned int *dhist = (unsigned int *)
-					p->sget("hist", 65536 * 4);
-				unsigned long long *dthr =
-					(unsigned long long *) p->sget("thr", 8);
-				uint64_t cap = hstats[0] + 1;	/* <= n_groups */
-				gg_q3_result_row *dout = (gg_q3_result_row *)
-					p->sget("cand",
-						cap * sizeof(gg_q3_result_row));
-				unsigned long long ncand = 0;
+				gg_q3_result_row row;
 
-				if (!dhist || !dthr || !dout)
-					return fail(GG_ENOMEM, "topk scratch");
-				GG_HIP(hipMemsetAsync(dhist, 0, 65536 * 4,
-						      e.stream));
-				GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-				if (ord_dlen)
-				{
-					GG_HIP(launch_dn_q3_hist(
-						e.stream, ordd_pr, ord_dlen,
-						stats5, dhist));
-					GG_HIP(launch_q3_threshold(
-						e.stream, dhist, stats5, k,
-						dthr));
-					GG_HIP(launch_dn_q3_collect(
-						e.stream, ordd_pr,
-						ord_dlen, dthr, dout, ctr,
-						cap));
-				}
-				else
-				{
-					GG_HIP(launch_q3_hist(e.stream, ord,
-							      stats5, dhist));
-					GG_HIP(launch_q3_threshold(
-						e.stream, dhist, stats5, k,
-						dthr));
-					GG_HIP(launch_q3_collect(
-						e.stream, ord, dthr, dout,
-						ctr, cap));
-				}
-				GG_HIP(hipStreamSynchronize(e.stream));
-				GG_TRY(read_counter(ctr, &ncand));
-				if (ncand > cap)
-					return fail(GG_EINVAL,
-						    "top-k candidate overflow (%llu)",
-						    ncand);
-				cand.resize(ncand);
-				if (ncand)
-					GG_HIP(hipMemcpy(
-						cand.data(), dout,
-						ncand * sizeof(gg_q3_result_row),
-						hipMemcpyDeviceToHost));
+				std::memcpy(&row, &v[5 + i * 4], 32);
+				if (row.rev_lo || row.rev_hi)
+					cand.push_back(row);
 			}
 		}
 		std::sort(cand.begin(), cand.end(), Q3TopkCmp());
 		if ((int64_t) cand.size() > k)
 			cand.resize(k);
-
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("q3_topk");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += (int64_t) hstats[0];
-		st.rows_out += (int64_t) cand.size();
-		/* dominant traffic: one 8 B/slot sweep of the dense rev
-		 * array (survivor finish pass is ~ngroups gathers) */
-		st.hbm_bytes += ord_dlen ? ord_dlen * 8
-			: (int64_t) ord.nslots * 16;
-
-		/* 5. global combine (the Gather Motion to the QD:
-		 * nodeMotion gather + final-stage combine) */
-		u128 revsum = ((u128) hstats[1]) | ((u128) hstats[2] << 64);
-		uint64_t ngroups = hstats[0];
-		uint64_t checksum = hstats[3];
-		uint64_t njoin_g = njoin;
-
-		if (nseg > 1)
-		{
-			size_t per = 5 + (size_t) k * 4;
-			std::vector<unsigned long long> lbuf(per, 0);
-
-			lbuf[0] = ngroups;
-			lbuf[1] = (uint64_t) revsum;
-			lbuf[2] = (uint64_t) (revsum >> 64);
-			lbuf[3] = njoin_g;
-			lbuf[4] = checksum;
-			for (size_t i = 0; i < cand.size(); i++)
-				std::memcpy(&lbuf[5 + i * 4], &cand[i], 32);
-
-			unsigned long long *g = (unsigned long long *)
-				p->sget("gatherg", (per + per * (size_t) nseg) * 8);
-
-			if (!g)
-				return fail(GG_ENOMEM, "gather scratch");
-			GG_HIP(hipMemcpy(g, lbuf.data(), per * 8,
-					 hipMemcpyHostToDevice));
-			GG_TRY(comm_allgather_u64(g, g + per, per));
-			std::vector<unsigned long long> all(per * (size_t) nseg);
-
-			GG_HIP(hipMemcpy(all.data(), g + per, all.size() * 8,
-					 hipMemcpyDeviceToHost));
-
-			ngroups = 0;
-			revsum = 0;
-			checksum = 0;
-			njoin_g = 0;
-			cand.clear();
-			for (int r = 0; r < nseg; r++)
-			{
-				const unsigned long long *v =
-					&all[per * (size_t) r];
-
-				ngroups += v[0];
-				revsum += ((u128) v[1]) | ((u128) v[2] << 64);
-				njoin_g += v[3];
-				checksum += v[4];
-				for (int64_t i = 0; i < k; i++)
-				{
-					gg_q3_result_row row;
-
-					std::memcpy(&row, &v[5 + i * 4], 32);
-					if (row.rev_lo || row.rev_hi)
-						cand.push_back(row);
-				}
-			}
-			std::sort(cand.begin(), cand.end(), Q3TopkCmp());
-			if ((int64_t) cand.size() > k)
-				cand.resize(k);
-		}
-
-		gg_q3_result_hdr *hdr = (gg_q3_result_hdr *) arena;
-
-		hdr->n_out = (int64_t) cand.size();
-		hdr->n_groups = (int64_t) ngroups;
-		hdr->rev_sum_lo = (uint64_t) revsum;
-		hdr->rev_sum_hi = (int64_t) (revsum >> 64);
-		hdr->group_checksum = checksum;
-		hdr->n_join_rows = (int64_t) njoin_g;
-		std::memcpy(hdr + 1, cand.data(),
-			    cand.size() * sizeof(gg_q3_result_row));
-		*written = sizeof(*hdr) +
-			cand.size() * sizeof(gg_q3_result_row);
 	}
+
+	gg_q3_result_hdr *hdr = (gg_q3_result_hdr *) arena;
+
+	hdr->n_out = (int64_t) cand.size();
+	hdr->n_groups = (int64_t) ngroups;
+	hdr->rev_sum_lo = (uint64_t) revsum;
+	hdr->rev_sum_hi = (int64_t) (revsum >> 64);
+	hdr->group_checksum = checksum;
+	hdr->n_join_rows = (int64_t) njoin_g;
+	std::memcpy(hdr + 1, cand.data(),
+		    cand.size() * sizeof(gg_q3_result_row));
+	*written = sizeof(*hdr) + cand.size() * sizeof(gg_q3_result_row);
 	return GG_OK;
+}
+
+static gg_status exec_q3(Pipeline *p, void *arena, size_t bytes,
+			 size_t *written)
+{
+	Q3State S{};
+
+	S.p = p;
+	S.li = get_table(p->desc.lineitem);
+	S.od = get_table(p->desc.orders);
+	S.cu = get_table(p->desc.customer);
+	S.k = p->desc.limit_k > 0 ? p->desc.limit_k : 10;
+	/* the Motion-exchange path normally runs for nseg > 1; the env
+	 * knob forces it at nseg == 1 (self-loopback over RCCL) so the
+	 * whole redistribute plumbing is testable on one GPU */
+	S.exch = engine().cfg.n_segments > 1 ||
+		getenv("GG_FORCE_EXCHANGE") != nullptr;
+
+	if (bytes < sizeof(gg_q3_result_hdr) +
+	    (size_t) S.k * sizeof(gg_q3_result_row))
+		return fail(GG_EINVAL, "arena too small");
+	if (S.k > 1000)
+		return fail(GG_ENOTSUP, "LIMIT > 1000 not supported in v1");
+
+	S.c_ck = (const int64_t *) S.cu->col("custkey");
+	S.c_ms = (const uint8_t *) S.cu->col("mktseg");
+	S.o_ok = (const int64_t *) S.od->col("orderkey");
+	S.o_ck = (const int64_t *) S.od->col("custkey");
+	S.o_dt = (const int32_t *) S.od->col("orderdate");
+	S.o_pr = (const int32_t *) S.od->col("shippriority");
+	S.l_ok = (const int64_t *) S.li->col("orderkey");
+	S.l_sd = (const int32_t *) S.li->col("shipdate");
+	S.l_pc = (const int64_t *) S.li->col("price");
+	S.l_dc = (const int64_t *) S.li->col("disc");
+	if (!S.c_ck || !S.c_ms || !S.o_ok || !S.o_ck || !S.o_dt || !S.o_pr ||
+	    !S.l_ok || !S.l_sd || !S.l_pc || !S.l_dc)
+		return fail(GG_EINVAL, "Q3: missing column");
+
+	S.cutoff = p->desc.cutoff_date;
+	S.segcode = p->desc.mktsegment;
+	S.ctr = (unsigned long long *) p->sget("ctr", 8);
+	if (!S.ctr)
+		return fail(GG_ENOMEM, "scratch");
+
+	GG_TRY(q3_build_customer(S));
+	GG_TRY(q3_orders_layout(S));
+	GG_TRY(S.exch ? q3_orders_exchange(S) : q3_build_orders_local(S));
+	GG_TRY(q3_probe_lineitem(S));
+	GG_TRY(q3_select_topk(S));
+	return q3_combine(S, arena, written);
 }
 
 /* ---------------- execution: Q5 (mpph5) ---------------- */
@@ -2472,764 +2347,515 @@ struct Q5RowCmp
 	}
 };
 
-static gg_status exec_q5(Pipeline *p, void *arena, size_t bytes,
-			 size_t *written)
+/* what the steps of one Q5 execute hand each other */
+struct Q5State
 {
-	Engine &e = engine();
-	Table *li = get_table(p->desc.lineitem);
-	Table *od = get_table(p->desc.orders);
-	Table *cu = get_table(p->desc.customer);
-	Table *su = get_table(p->desc.supplier);
-	Table *na = get_table(p->desc.nation);
-	int nseg = e.cfg.n_segments;
-	int me = e.cfg.segment_id;
-	bool exch = nseg > 1 || getenv("GG_FORCE_EXCHANGE") != nullptr;
+	Pipeline *p;
+	Table *li, *od, *cu, *su, *na;
+	bool exch;
+	int32_t date_lo, date_hi;
+	uint8_t regionkey;
+	const int64_t *l_ok, *l_sk, *l_pc, *l_dc, *o_ok, *o_ck, *c_ck, *s_sk;
+	const int32_t *o_dt, *n_nk, *n_rk;
+	const uint8_t *c_nk, *s_nk;
+	unsigned long long *ctr;	/* 8-byte device counter */
 
-	if (bytes < sizeof(gg_q5_result_hdr) +
-	    GG_NNATIONS * sizeof(gg_q5_result_row))
-		return fail(GG_EINVAL, "arena too small");
+	uint8_t *region_of = nullptr;	/* device u8 region_of[nation] */
 
-	const int64_t *l_ok = (const int64_t *) li->col("orderkey");
-	const int64_t *l_sk = (const int64_t *) li->col("suppkey");
-	const int64_t *l_pc = (const int64_t *) li->col("price");
-	const int64_t *l_dc = (const int64_t *) li->col("disc");
-	const int64_t *o_ok = (const int64_t *) od->col("orderkey");
-	const int64_t *o_ck = (const int64_t *) od->col("custkey");
-	const int32_t *o_dt = (const int32_t *) od->col("orderdate");
-	const int64_t *c_ck = (const int64_t *) cu->col("custkey");
-	const uint8_t *c_nk = (const uint8_t *) cu->col("nationkey");
-	const int64_t *s_sk = (const int64_t *) su->col("suppkey");
-	const uint8_t *s_nk = (const uint8_t *) su->col("nationkey");
-	const int32_t *n_nk = (const int32_t *) na->col("nationkey");
-	const int32_t *n_rk = (const int32_t *) na->col("regionkey");
-
-	if (!l_ok || !l_sk || !l_pc || !l_dc || !o_ok || !o_ck || !o_dt ||
-	    !c_ck || !c_nk || !s_sk || !s_nk || !n_nk || !n_rk)
-		return fail(GG_EINVAL, "Q5: missing column");
-
-	int32_t date_lo = p->desc.cutoff_date;
-	int32_t date_hi = p->desc.cutoff_hi;
-	uint8_t regionkey = p->desc.regionkey;
-	unsigned long long *ctr =
-		(unsigned long long *) p->sget("ctr", 8);
-
-	if (!ctr)
-		return fail(GG_ENOMEM, "scratch");
-
-	/* nation dim (25 rows) → host → device u8 region_of[25]; the
-	 * region⋈nation semi-join resolved here, the broadcast-Motion
-	 * analog for the tiny dims */
-	uint8_t region_of_h[GG_NNATIONS];
-	{
-		std::vector<int32_t> nk(na->nrows), rk(na->nrows);
-
-		GG_HIP(hipMemcpy(nk.data(), n_nk, na->nrows * 4,
-				 hipMemcpyDeviceToHost));
-		GG_HIP(hipMemcpy(rk.data(), n_rk, na->nrows * 4,
-				 hipMemcpyDeviceToHost));
-		std::memset(region_of_h, 0xff, sizeof(region_of_h));
-		for (int64_t i = 0; i < na->nrows; i++)
-			if (nk[i] >= 0 && nk[i] < GG_NNATIONS)
-				region_of_h[nk[i]] = (uint8_t) rk[i];
-	}
-	uint8_t *region_of = (uint8_t *) p->sget("region_of", 32);
-
-	if (!region_of)
-		return fail(GG_ENOMEM, "region_of");
-	GG_HIP(hipMemcpy(region_of, region_of_h, GG_NNATIONS,
-			 hipMemcpyHostToDevice));
-
-	/* 1. customer map: c_custkey → c_nationkey.  Dense custkeys use a
-	 * u8 nation array (255 = absent) in L2/L3; hash map fallback. */
+	/* customer map c_custkey → c_nationkey: u8 array or hash map */
 	DeviceHashTable cust{};
 	uint8_t *cust_dense = nullptr;
 	int64_t cust_dlen = 0;
-	{
-		unsigned long long maxk = 0;
 
-		GG_TRY(cached_max_i64(e, p, c_ck, cu->nrows, ctr, &maxk));
-		if (cu->nrows > 0 && maxk > 0 &&
-		    maxk <= (unsigned long long) (8 * cu->nrows + 16))
-			cust_dlen = (int64_t) maxk + 1;
-	}
-	p->stat(cust_dlen ? "path_cust_dense" : "path_cust_hash").launches++;
-	{
-		Timed tm(e.stream);
-
-		if (cust_dlen)
-		{
-			cust_dense = (uint8_t *)
-				p->sget("cust.dense", (size_t) cust_dlen);
-			if (!cust_dense)
-				return fail(GG_ENOMEM, "cust dense");
-			GG_HIP(hipMemsetAsync(cust_dense, 0xff,
-					      (size_t) cust_dlen, e.stream));
-			GG_HIP(launch_cust_dense_fill_nat(e.stream, c_ck,
-							  c_nk, cu->nrows,
-							  cust_dense,
-							  cust_dlen));
-		}
-		else
-		{
-			if (!p->cust_slots)
-				p->cust_slots =
-					next_pow2(2 * (uint64_t) (cu->nrows + 1));
-			cust.nslots = p->cust_slots;
-			cust.keys = (unsigned long long *)
-				p->sget("cust.keys", cust.nslots * 8);
-			cust.payload = (unsigned long long *)
-				p->sget("cust.pay", cust.nslots * 8);
-			if (!cust.keys || !cust.payload)
-				return fail(GG_ENOMEM, "cust map");
-			GG_HIP(hipMemsetAsync(cust.keys, 0, cust.nslots * 8,
-					      e.stream));
-			GG_HIP(launch_build_kv(e.stream, c_ck, c_nk,
-					       cu->nrows, cust));
-		}
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("build_customer_map");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += cu->nrows;
-		st.hbm_bytes += cu->nrows * 9;
-	}
-
-	/* 2. supplier table: s_suppkey → s_nationkey, in-region only.
-	 * Dense keys (max <= 8x rows) use a u8 direct-map array in L2 —
-	 * one byte load replaces bloom+table probes; hash fallback kept
-	 * for sparse keys. */
+	/* in-region suppliers s_suppkey → s_nationkey */
 	DeviceHashTable supp{};
 	uint8_t *supp_dense = nullptr;
 	int64_t supp_dense_len = 0;
-	{
-		unsigned long long maxk = 0;
 
-		GG_TRY(cached_max_i64(e, p, s_sk, su->nrows, ctr, &maxk));
-		if (su->nrows > 0 && maxk > 0 &&
-		    maxk <= (unsigned long long) (8 * su->nrows + 16))
-			supp_dense_len = (int64_t) maxk + 1;
-	}
-	{
-		Timed tm(e.stream);
-
-		if (supp_dense_len && !exch)
-		{
-			supp_dense = (uint8_t *)
-				p->sget("supp.dense", (size_t) supp_dense_len);
-			if (!supp_dense)
-				return fail(GG_ENOMEM, "supp dense");
-			GG_HIP(hipMemsetAsync(supp_dense, 0xff,
-					      (size_t) supp_dense_len,
-					      e.stream));
-			GG_HIP(launch_supp_dense_fill(e.stream, s_sk, s_nk,
-						      su->nrows, region_of,
-						      regionkey, supp_dense,
-						      supp_dense_len));
-			GG_HIP(hipStreamSynchronize(e.stream));
-		}
-		else if (!exch)
-		{
-			if (!p->supp_slots)
-				p->supp_slots =
-					next_pow2(2 * (uint64_t) (su->nrows + 1));
-			supp.nslots = p->supp_slots;
-			supp.bloom_words = supp.nslots / 8 < 1024
-				? 1024 : supp.nslots / 8;
-			supp.keys = (unsigned long long *)
-				p->sget("supp.keys", supp.nslots * 8);
-			supp.payload = (unsigned long long *)
-				p->sget("supp.pay", supp.nslots * 8);
-			supp.bloom = (unsigned long long *)
-				p->sget("supp.bloom", supp.bloom_words * 8);
-			if (!supp.keys || !supp.payload || !supp.bloom)
-				return fail(GG_ENOMEM, "supp table");
-			GG_HIP(hipMemsetAsync(supp.keys, 0, supp.nslots * 8,
-					      e.stream));
-			GG_HIP(hipMemsetAsync(supp.bloom, 0,
-					      supp.bloom_words * 8, e.stream));
-			GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-			GG_HIP(launch_build_supp(e.stream, s_sk, s_nk,
-						 su->nrows, region_of,
-						 regionkey, supp, ctr));
-			GG_HIP(hipStreamSynchronize(e.stream));
-		}
-		else
-		{
-			/* broadcast Motion of the small dim: compact the
-			 * local in-region shard, allgather (padded), insert
-			 * every rank's rows locally */
-			if (!comm_ready())
-				return fail(GG_ESTATE,
-					    "exchange path requires comm");
-			unsigned long long nkept = 0;
-			int64_t *csk = (int64_t *) p->sget("supp.csk",
-							   (su->nrows + 1) * 8);
-			int64_t *csn = (int64_t *) p->sget("supp.csn",
-							   (su->nrows + 1) * 8);
-
-			if (!csk || !csn)
-				return fail(GG_ENOMEM, "supp compact");
-			GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-			GG_HIP(launch_supp_filter_compact(e.stream, s_sk, s_nk,
-							  su->nrows, region_of,
-							  regionkey, csk, csn,
-							  ctr));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(read_counter(ctr, &nkept));
-
-			/* exchange counts */
-			std::vector<unsigned long long> counts(nseg);
-			{
-				unsigned long long *g = (unsigned long long *)
-					p->sget("supp.cnt", (1 + (size_t) nseg) * 8);
-
-				if (!g)
-					return fail(GG_ENOMEM, "supp cnt");
-				GG_HIP(hipMemcpy(g, &nkept, 8,
-						 hipMemcpyHostToDevice));
-				GG_TRY(comm_allgather_u64(g, g + 1, 1));
-				GG_HIP(hipMemcpy(counts.data(), g + 1,
-						 (size_t) nseg * 8,
-						 hipMemcpyDeviceToHost));
-			}
-			unsigned long long maxc = 0, total = 0;
-
-			for (int r = 0; r < nseg; r++)
-			{
-				total += counts[r];
-				if (counts[r] > maxc)
-					maxc = counts[r];
-			}
-			/* padded allgather of (sk, sn) pairs */
-			uint64_t per = 2 * (maxc + 1);
-			int64_t *gs = (int64_t *)
-				p->sget("supp.gather",
-					(per + per * (size_t) nseg) * 8);
-
-			if (!gs)
-				return fail(GG_ENOMEM, "supp gather");
-			GG_HIP(hipMemcpyAsync(gs, csk, (nkept + 1) * 8,
-					      hipMemcpyDeviceToDevice, e.stream));
-			GG_HIP(hipMemcpyAsync(gs + (maxc + 1), csn,
-					      (nkept + 1) * 8,
-					      hipMemcpyDeviceToDevice, e.stream));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(comm_allgather_u64(gs, gs + per, per));
-
-			if (!p->supp_slots)
-				p->supp_slots = next_pow2(2 * (total + 1));
-			supp.nslots = p->supp_slots;
-			supp.bloom_words = supp.nslots / 8 < 1024
-				? 1024 : supp.nslots / 8;
-			supp.keys = (unsigned long long *)
-				p->sget("supp.keys", supp.nslots * 8);
-			supp.payload = (unsigned long long *)
-				p->sget("supp.pay", supp.nslots * 8);
-			supp.bloom = (unsigned long long *)
-				p->sget("supp.bloom", supp.bloom_words * 8);
-			if (!supp.keys || !supp.payload || !supp.bloom)
-				return fail(GG_ENOMEM, "supp table");
-			GG_HIP(hipMemsetAsync(supp.keys, 0, supp.nslots * 8,
-					      e.stream));
-			GG_HIP(hipMemsetAsync(supp.bloom, 0,
-					      supp.bloom_words * 8, e.stream));
-			for (int r = 0; r < nseg; r++)
-			{
-				int64_t *base = gs + per + (size_t) r * per;
-
-				if (counts[r])
-					GG_HIP(launch_insert_supp(
-						e.stream, base,
-						base + (maxc + 1),
-						(int64_t) counts[r], supp));
-			}
-			/* dense direct-map over the gathered pairs too,
-			 * but only after checking the GLOBAL max key stays
-			 * within the density bound (the pre-exchange check
-			 * saw only the local shard) */
-			supp_dense_len = 0;
-			{
-				unsigned long long gmax = 0;
-
-				GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-				for (int r = 0; r < nseg; r++)
-				{
-					int64_t *base =
-						gs + per + (size_t) r * per;
-
-					if (counts[r])
-						GG_HIP(launch_max_i64(
-							e.stream, base,
-							(int64_t) counts[r],
-							ctr));
-				}
-				GG_HIP(hipStreamSynchronize(e.stream));
-				GG_TRY(read_counter(ctr, &gmax));
-				if (gmax > 0 && (int64_t) gmax <=
-				    8 * su->nrows * (int64_t) nseg + 16)
-					supp_dense_len = (int64_t) gmax + 1;
-			}
-			if (supp_dense_len)
-			{
-				supp_dense = (uint8_t *)
-					p->sget("supp.dense",
-						(size_t) supp_dense_len);
-				if (!supp_dense)
-					return fail(GG_ENOMEM, "supp dense");
-				GG_HIP(hipMemsetAsync(supp_dense, 0xff,
-						      (size_t) supp_dense_len,
-						      e.stream));
-				for (int r = 0; r < nseg; r++)
-				{
-					int64_t *base =
-						gs + per + (size_t) r * per;
-
-					if (counts[r])
-						GG_HIP(launch_supp_dense_fill_pairs(
-							e.stream, base,
-							base + (maxc + 1),
-							(int64_t) counts[r],
-							supp_dense,
-							supp_dense_len));
-				}
-			}
-			GG_HIP(hipStreamSynchronize(e.stream));
-		}
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("build_supplier");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += su->nrows;
-		st.hbm_bytes += su->nrows * 9;	/* suppkey 8 + nation 1 */
-	}
-
-	/* 3. orders → okey → c_nationkey map.  Dense o_orderkey (with a
-	 * dense supplier side) uses the direct-map arrays (q3_dense.hip);
-	 * hash table fallback otherwise. */
+	/* orders o_orderkey → c_nationkey */
 	DeviceHashTable ord{};
 	uint8_t *ordd_pay8 = nullptr;
 	int64_t ord_dlen = 0;
 	unsigned long long nmatch = 0;
 
-	if (supp_dense)
-	{
-		unsigned long long maxk = 0;
+	unsigned long long *acc = nullptr;	/* [nation](count, lo, hi) */
+};
 
-		GG_TRY(cached_max_i64(e, p, o_ok, od->nrows, ctr, &maxk));
-		if (od->nrows > 0 && maxk > 0 &&
-		    maxk <= (unsigned long long) (8 * od->nrows + 16))
-			ord_dlen = (int64_t) maxk + 1;
+/* nation dim (25 rows) → host → device u8 region_of[25]; the
+ * region⋈nation semi-join resolved here, the broadcast-Motion
+ * analog for the tiny dims */
+static gg_status q5_nation_dim(Q5State &S)
+{
+	int64_t nrows = S.na->nrows;
+	uint8_t region_of_h[GG_NNATIONS];
+	std::vector<int32_t> nk(nrows), rk(nrows);
+
+	GG_HIP(hipMemcpy(nk.data(), S.n_nk, nrows * 4, hipMemcpyDeviceToHost));
+	GG_HIP(hipMemcpy(rk.data(), S.n_rk, nrows * 4, hipMemcpyDeviceToHost));
+	std::memset(region_of_h, 0xff, sizeof(region_of_h));
+	for (int64_t i = 0; i < nrows; i++)
+		if (nk[i] >= 0 && nk[i] < GG_NNATIONS)
+			region_of_h[nk[i]] = (uint8_t) rk[i];
+	S.region_of = (uint8_t *) S.p->sget("region_of", 32);
+	if (!S.region_of)
+		return fail(GG_ENOMEM, "region_of");
+	GG_HIP(hipMemcpy(S.region_of, region_of_h, GG_NNATIONS,
+			 hipMemcpyHostToDevice));
+	return GG_OK;
+}
+
+/* 1. customer map: c_custkey → c_nationkey.  Dense custkeys use a
+ * u8 nation array (255 = absent) in L2/L3; hash map fallback. */
+static gg_status q5_build_customer_map(Q5State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.cu->nrows;
+
+	GG_TRY(dense_key_len(e, p, S.c_ck, nrows, S.ctr, &S.cust_dlen));
+	p->stat(S.cust_dlen ? "path_cust_dense" : "path_cust_hash").launches++;
+
+	Timed tm(e.stream);
+
+	if (S.cust_dlen)
+	{
+		S.cust_dense = (uint8_t *)
+			p->sget("cust.dense", (size_t) S.cust_dlen);
+		if (!S.cust_dense)
+			return fail(GG_ENOMEM, "cust dense");
+		GG_HIP(hipMemsetAsync(S.cust_dense, 0xff,
+				      (size_t) S.cust_dlen, e.stream));
+		GG_HIP(launch_cust_dense_fill_nat(e.stream, S.c_ck, S.c_nk,
+						  nrows, S.cust_dense,
+						  S.cust_dlen));
 	}
-	p->stat(ord_dlen ? "path_orders_dense" : "path_orders_hash").launches++;
-	if (ord_dlen)
+	else
 	{
-		/* nation fits a byte; 255 = no matching order.  The u8 map
-		 * is its own membership filter — no Bloom reads on probe. */
-		ordd_pay8 = (uint8_t *)
-			p->sget("ordd.pay8", (size_t) ord_dlen);
-		if (!ordd_pay8)
-			return fail(GG_ENOMEM, "ord dense");
-		GG_HIP(hipMemsetAsync(ordd_pay8, 0xff, (size_t) ord_dlen,
-				      e.stream));
+		if (!p->cust_slots)
+			p->cust_slots = next_pow2(2 * (uint64_t) (nrows + 1));
+		GG_TRY(hash_table_alloc(p, "cust", p->cust_slots, HT_PAYLOAD,
+					&S.cust));
+		GG_HIP(launch_build_kv(e.stream, S.c_ck, S.c_nk, nrows,
+				       S.cust));
 	}
+	p->stat("build_customer_map").add(tm.stop(), nrows, 0, nrows * 9);
+	return GG_OK;
+}
 
-	if (!exch)
+/* the supplier hash table (sized once per pipeline) */
+static gg_status q5_supp_table(Q5State &S, uint64_t nkeys)
+{
+	if (!S.p->supp_slots)
+		S.p->supp_slots = next_pow2(2 * (nkeys + 1));
+	return hash_table_alloc(S.p, "supp", S.p->supp_slots,
+				HT_PAYLOAD | HT_BLOOM, &S.supp);
+}
+
+/* the supplier direct map, every byte 255 = absent */
+static gg_status q5_supp_dense_alloc(Q5State &S)
+{
+	S.supp_dense = (uint8_t *)
+		S.p->sget("supp.dense", (size_t) S.supp_dense_len);
+	if (!S.supp_dense)
+		return fail(GG_ENOMEM, "supp dense");
+	GG_HIP(hipMemsetAsync(S.supp_dense, 0xff, (size_t) S.supp_dense_len,
+			      engine().stream));
+	return GG_OK;
+}
+
+/* 2a. supplier table from this segment's rows alone */
+static gg_status q5_supplier_local(Q5State &S)
+{
+	Engine &e = engine();
+	int64_t nrows = S.su->nrows;
+
+	if (S.supp_dense_len)
 	{
-		Timed tm(e.stream);
+		GG_TRY(q5_supp_dense_alloc(S));
+		GG_HIP(launch_supp_dense_fill(e.stream, S.s_sk, S.s_nk, nrows,
+					      S.region_of, S.regionkey,
+					      S.supp_dense,
+					      S.supp_dense_len));
+	}
+	else
+	{
+		GG_TRY(q5_supp_table(S, (uint64_t) nrows));
+		GG_HIP(hipMemsetAsync(S.ctr, 0, 8, e.stream));
+		GG_HIP(launch_build_supp(e.stream, S.s_sk, S.s_nk, nrows,
+					 S.region_of, S.regionkey, S.supp,
+					 S.ctr));
+	}
+	GG_HIP(hipStreamSynchronize(e.stream));
+	return GG_OK;
+}
 
-		if (ord_dlen)
-		{
-			GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-			GG_HIP(launch_dn_build_orders_q5_u8(
-				e.stream, o_ok, o_ck, o_dt, od->nrows,
-				date_lo, date_hi, cust, cust_dense, cust_dlen,
-				ordd_pay8, ord_dlen, ctr));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(read_counter(ctr, &nmatch));
-			double ms0 = tm.stop();
-			KernelStatAcc &st0 = p->stat("build_orders_q5");
+/* 2b. broadcast Motion of the small dim: compact the local in-region
+ * shard, allgather (padded), insert every rank's rows locally */
+static gg_status q5_supplier_broadcast(Q5State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	const int nseg = e.cfg.n_segments;
+	int64_t nrows = S.su->nrows;
 
-			st0.launches++;
-			st0.total_ms += ms0;
-			st0.rows_in += od->nrows;
-			st0.rows_out += (int64_t) nmatch;
-			st0.hbm_bytes += od->nrows * 20;  /* okey,ckey,odate */
-			goto orders_done;
-		}
+	if (!comm_ready())
+		return fail(GG_ESTATE, "exchange path requires comm");
+	unsigned long long nkept = 0;
+	int64_t *csk = (int64_t *) p->sget("supp.csk", (nrows + 1) * 8);
+	int64_t *csn = (int64_t *) p->sget("supp.csn", (nrows + 1) * 8);
+
+	if (!csk || !csn)
+		return fail(GG_ENOMEM, "supp compact");
+	GG_TRY(run_counted(e.stream, S.ctr, &nkept, [&] {
+		return launch_supp_filter_compact(
+			e.stream, S.s_sk, S.s_nk, nrows, S.region_of,
+			S.regionkey, csk, csn, S.ctr);
+	}));
+
+	/* exchange counts */
+	std::vector<unsigned long long> counts;
+	unsigned long long maxc = 0, total = 0;
+
+	GG_TRY(allgather_host_u64(p, "supp.cnt", &nkept, 1, counts));
+	for (int r = 0; r < nseg; r++)
+	{
+		total += counts[r];
+		if (counts[r] > maxc)
+			maxc = counts[r];
+	}
+	/* padded allgather of (sk, sn) pairs */
+	uint64_t per = 2 * (maxc + 1);
+	int64_t *gs = (int64_t *)
+		p->sget("supp.gather", (per + per * (size_t) nseg) * 8);
+
+	if (!gs)
+		return fail(GG_ENOMEM, "supp gather");
+	GG_HIP(hipMemcpyAsync(gs, csk, (nkept + 1) * 8,
+			      hipMemcpyDeviceToDevice, e.stream));
+	GG_HIP(hipMemcpyAsync(gs + (maxc + 1), csn, (nkept + 1) * 8,
+			      hipMemcpyDeviceToDevice, e.stream));
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_TRY(comm_allgather_u64(gs, gs + per, per));
+
+	/* rank r's gathered suppkeys; its nations follow maxc + 1 later */
+	auto rank_sk = [&](int r) { return gs + per + (size_t) r * per; };
+
+	GG_TRY(q5_supp_table(S, total));
+	for (int r = 0; r < nseg; r++)
+		if (counts[r])
+			GG_HIP(launch_insert_supp(e.stream, rank_sk(r),
+						  rank_sk(r) + (maxc + 1),
+						  (int64_t) counts[r],
+						  S.supp));
+	/* dense direct-map over the gathered pairs too,
+	 * but only after checking the GLOBAL max key stays
+	 * within the density bound (the pre-exchange check
+	 * saw only the local shard).  Not dense_key_len(): the max
+	 * runs over gathered pairs, not a cached column, and its bound
+	 * counts every segment's rows. */
+	unsigned long long gmax = 0;
+
+	S.supp_dense_len = 0;
+	GG_HIP(hipMemsetAsync(S.ctr, 0, 8, e.stream));
+	for (int r = 0; r < nseg; r++)
+		if (counts[r])
+			GG_HIP(launch_max_i64(e.stream, rank_sk(r),
+					      (int64_t) counts[r], S.ctr));
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_TRY(read_counter(S.ctr, &gmax));
+	if (gmax > 0 && (int64_t) gmax <= 8 * nrows * (int64_t) nseg + 16)
+		S.supp_dense_len = (int64_t) gmax + 1;
+	if (S.supp_dense_len)
+	{
+		GG_TRY(q5_supp_dense_alloc(S));
+		for (int r = 0; r < nseg; r++)
+			if (counts[r])
+				GG_HIP(launch_supp_dense_fill_pairs(
+					e.stream, rank_sk(r),
+					rank_sk(r) + (maxc + 1),
+					(int64_t) counts[r], S.supp_dense,
+					S.supp_dense_len));
+	}
+	GG_HIP(hipStreamSynchronize(e.stream));
+	return GG_OK;
+}
+
+/* 2. supplier table: s_suppkey → s_nationkey, in-region only.
+ * Dense keys (max <= 8x rows) use a u8 direct-map array in L2 —
+ * one byte load replaces bloom+table probes; hash fallback kept
+ * for sparse keys. */
+static gg_status q5_build_supplier(Q5State &S)
+{
+	Engine &e = engine();
+	int64_t nrows = S.su->nrows;
+
+	GG_TRY(dense_key_len(e, S.p, S.s_sk, nrows, S.ctr,
+			     &S.supp_dense_len));
+	Timed tm(e.stream);
+
+	GG_TRY(S.exch ? q5_supplier_broadcast(S) : q5_supplier_local(S));
+	/* suppkey 8 + nation 1 */
+	S.p->stat("build_supplier").add(tm.stop(), nrows, 0, nrows * 9);
+	return GG_OK;
+}
+
+/* 3. orders → okey → c_nationkey map.  Dense o_orderkey (with a
+ * dense supplier side) uses the direct-map arrays (q3_dense.hip);
+ * hash table fallback otherwise.  This step picks the layout and readies
+ * the dense array; the build (local) or the exchange fills it. */
+static gg_status q5_orders_layout(Q5State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+
+	if (S.supp_dense)
+		GG_TRY(dense_key_len(e, p, S.o_ok, S.od->nrows, S.ctr,
+				     &S.ord_dlen));
+	p->stat(S.ord_dlen ? "path_orders_dense" : "path_orders_hash").launches++;
+	if (!S.ord_dlen)
+		return GG_OK;
+	/* nation fits a byte; 255 = no matching order.  The u8 map
+	 * is its own membership filter — no Bloom reads on probe. */
+	S.ordd_pay8 = (uint8_t *) p->sget("ordd.pay8", (size_t) S.ord_dlen);
+	if (!S.ordd_pay8)
+		return fail(GG_ENOMEM, "ord dense");
+	GG_HIP(hipMemsetAsync(S.ordd_pay8, 0xff, (size_t) S.ord_dlen,
+			      e.stream));
+	return GG_OK;
+}
+
+/* 3a. orders build, single segment */
+static gg_status q5_build_orders_local(Q5State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.od->nrows;
+	Timed tm(e.stream);
+
+	if (S.ord_dlen)
+		GG_TRY(run_counted(e.stream, S.ctr, &S.nmatch, [&] {
+			return launch_dn_build_orders_q5_u8(
+				e.stream, S.o_ok, S.o_ck, S.o_dt, nrows,
+				S.date_lo, S.date_hi, S.cust, S.cust_dense,
+				S.cust_dlen, S.ordd_pay8, S.ord_dlen, S.ctr);
+		}));
+	else
+	{
 		if (!p->ord_slots)
 		{
 			unsigned long long nfil = 0;
 
-			GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-			GG_HIP(launch_count_date_range(e.stream, o_dt,
-						       od->nrows, date_lo,
-						       date_hi, ctr));
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(read_counter(ctr, &nfil));
+			GG_TRY(run_counted(e.stream, S.ctr, &nfil, [&] {
+				return launch_count_date_range(
+					e.stream, S.o_dt, nrows, S.date_lo,
+					S.date_hi, S.ctr);
+			}));
 			p->ord_slots = next_pow2(2 * (nfil + 1));
 		}
-		ord.nslots = p->ord_slots;
-		ord.bloom_words = ord.nslots / 8 < 1024 ? 1024 : ord.nslots / 8;
-		ord.keys = (unsigned long long *)
-			p->sget("ord.keys", ord.nslots * 8);
-		ord.payload = (unsigned long long *)
-			p->sget("ord.pay", ord.nslots * 8);
-		ord.bloom = (unsigned long long *)
-			p->sget("ord.bloom", ord.bloom_words * 8);
-		if (!ord.keys || !ord.payload || !ord.bloom)
-			return fail(GG_ENOMEM, "ord table");
-		GG_HIP(hipMemsetAsync(ord.keys, 0, ord.nslots * 8, e.stream));
-		GG_HIP(hipMemsetAsync(ord.bloom, 0, ord.bloom_words * 8,
-				      e.stream));
-		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-		GG_HIP(launch_build_orders_q5(e.stream, o_ok, o_ck, o_dt,
-					      od->nrows, date_lo, date_hi,
-					      cust, cust_dense, cust_dlen,
-					      ord, ctr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_TRY(read_counter(ctr, &nmatch));
-		{
-			double ms = tm.stop();
-			KernelStatAcc &st = p->stat("build_orders_q5");
-
-			st.launches++;
-			st.total_ms += ms;
-			st.rows_in += od->nrows;
-			st.rows_out += (int64_t) nmatch;
-			st.hbm_bytes += od->nrows * 20;  /* okey,ckey,odate */
-		}
-orders_done:;
+		GG_TRY(hash_table_alloc(p, "ord", p->ord_slots,
+					HT_PAYLOAD | HT_BLOOM, &S.ord));
+		GG_TRY(run_counted(e.stream, S.ctr, &S.nmatch, [&] {
+			return launch_build_orders_q5(
+				e.stream, S.o_ok, S.o_ck, S.o_dt, nrows,
+				S.date_lo, S.date_hi, S.cust, S.cust_dense,
+				S.cust_dlen, S.ord, S.ctr);
+		}));
 	}
+	/* okey, ckey, odate */
+	p->stat("build_orders_q5").add(tm.stop(), nrows, (int64_t) S.nmatch,
+				       nrows * 20);
+	return GG_OK;
+}
+
+/* 3b. orders build across segments: two Motion redistribute legs, as in
+ * Q3 but with the customer MAP payload (c_nationkey) */
+static gg_status q5_orders_exchange(Q5State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.od->nrows;
+
+	if (!comm_ready())
+		return fail(GG_ESTATE, "exchange path requires comm");
+	Timed tm(e.stream);
+	int64_t *f_ck = (int64_t *) p->sget("f_ck", (nrows + 1) * 8);
+	int64_t *f_ok = (int64_t *) p->sget("f_ok", (nrows + 1) * 8);
+	int64_t *f_pay = (int64_t *) p->sget("f_pay", (nrows + 1) * 8);
+	unsigned long long nfil = 0, nm = 0;
+
+	if (!f_ck || !f_ok || !f_pay)
+		return fail(GG_ENOMEM, "exchange scratch");
+	GG_TRY(run_counted(e.stream, S.ctr, &nfil, [&] {
+		return launch_orders_filter_compact(
+			e.stream, S.o_ok, S.o_ck, S.o_dt,
+			S.o_dt /* prio unused */, nrows, S.date_lo,
+			S.date_hi, f_ck, f_ok, f_pay, S.ctr);
+	}));
+
+	/* leg 1: filtered orders → owner of o_custkey */
+	const int64_t *in1[3] = {f_ck, f_ok, nullptr};
+	int64_t *r1[3];
+	uint64_t rtotal = 0;
+
+	GG_TRY(motion_redistribute(p, f_ck, in1, (int64_t) nfil, "leg1", r1,
+				   &rtotal));
+
+	/* probe local customer map → matched (okey, nation) */
+	int64_t *m_ok = (int64_t *) p->sget("m_ok", (rtotal + 1) * 8);
+	int64_t *m_nat = (int64_t *) p->sget("m_pay", (rtotal + 1) * 8);
+
+	if (!m_ok || !m_nat)
+		return fail(GG_ENOMEM, "match scratch");
+	GG_TRY(run_counted(e.stream, S.ctr, &nm, [&] {
+		return launch_probe_cust_map_compact(
+			e.stream, r1[0], r1[1], (int64_t) rtotal, S.cust,
+			S.cust_dense, S.cust_dlen, m_ok, m_nat, S.ctr);
+	}));
+
+	/* leg 2: matched orders → owner of o_orderkey */
+	const int64_t *in2[3] = {m_ok, m_nat, nullptr};
+	int64_t *r2[3];
+	uint64_t rtotal2 = 0;
+
+	GG_TRY(motion_redistribute(p, m_ok, in2, (int64_t) nm, "leg2", r2,
+				   &rtotal2));
+	S.nmatch = rtotal2;
+	if (S.ord_dlen)
+		GG_HIP(launch_dn_insert_orders_q5_u8(e.stream, r2[0], r2[1],
+						     (int64_t) rtotal2,
+						     S.ordd_pay8,
+						     S.ord_dlen));
 	else
 	{
-		/* two Motion redistribute legs, as in Q3 but with the
-		 * customer MAP payload (c_nationkey) */
-		if (!comm_ready())
-			return fail(GG_ESTATE, "exchange path requires comm");
-		Timed tm(e.stream);
-		int64_t *f_ck = (int64_t *) p->sget("f_ck", (od->nrows + 1) * 8);
-		int64_t *f_ok = (int64_t *) p->sget("f_ok", (od->nrows + 1) * 8);
-		int64_t *f_pay = (int64_t *) p->sget("f_pay", (od->nrows + 1) * 8);
-		unsigned long long *dcnt =
-			(unsigned long long *) p->sget("dcnt", (size_t) nseg * 8);
-		unsigned long long *doffs =
-			(unsigned long long *) p->sget("doffs", (size_t) nseg * 8);
-		unsigned long long nfil = 0;
-
-		if (!f_ck || !f_ok || !f_pay || !dcnt || !doffs)
-			return fail(GG_ENOMEM, "exchange scratch");
-		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-		GG_HIP(launch_orders_filter_compact(e.stream, o_ok, o_ck, o_dt,
-						    o_dt /* prio unused */,
-						    od->nrows, date_lo,
-						    date_hi, f_ck, f_ok,
-						    f_pay, ctr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_TRY(read_counter(ctr, &nfil));
-
-		std::vector<unsigned long long> cnts(nseg), offs(nseg + 1, 0);
-
-		GG_HIP(hipMemsetAsync(dcnt, 0, (size_t) nseg * 8, e.stream));
-		GG_HIP(launch_part_count(e.stream, f_ck, (int64_t) nfil, nseg,
-					 dcnt));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_HIP(hipMemcpy(cnts.data(), dcnt, (size_t) nseg * 8,
-				 hipMemcpyDeviceToHost));
-		for (int i = 0; i < nseg; i++)
-			offs[i + 1] = offs[i] + cnts[i];
-
-		int64_t *s_ckb = (int64_t *) p->sget("s_ck", (nfil + 1) * 8);
-		int64_t *s_okb = (int64_t *) p->sget("s_ok", (nfil + 1) * 8);
-
-		if (!s_ckb || !s_okb)
-			return fail(GG_ENOMEM, "send scratch");
-		GG_HIP(hipMemcpy(doffs, offs.data(), (size_t) nseg * 8,
-				 hipMemcpyHostToDevice));
-		GG_HIP(launch_part_scatter3(e.stream, f_ck, (int64_t) nfil,
-					    nseg, f_ck, f_ok, nullptr, doffs,
-					    s_ckb, s_okb, nullptr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-
-		std::vector<unsigned long long> allcnt((size_t) nseg * nseg);
-		{
-			unsigned long long *g = (unsigned long long *)
-				p->sget("cntg", (size_t) (nseg + nseg * nseg) * 8);
-
-			if (!g)
-				return fail(GG_ENOMEM, "cnt allgather");
-			GG_HIP(hipMemcpy(g, cnts.data(), (size_t) nseg * 8,
-					 hipMemcpyHostToDevice));
-			GG_TRY(comm_allgather_u64(g, g + nseg, nseg));
-			GG_HIP(hipMemcpy(allcnt.data(), g + nseg,
-					 allcnt.size() * 8,
-					 hipMemcpyDeviceToHost));
-		}
-		std::vector<unsigned long long> rcnts(nseg), roffs(nseg + 1, 0);
-
-		for (int s2 = 0; s2 < nseg; s2++)
-			rcnts[s2] = allcnt[(size_t) s2 * nseg + me];
-		for (int i = 0; i < nseg; i++)
-			roffs[i + 1] = roffs[i] + rcnts[i];
-		uint64_t rtotal = roffs[nseg];
-
-		int64_t *r_ck = (int64_t *) p->sget("r_ck", (rtotal + 1) * 8);
-		int64_t *r_ok = (int64_t *) p->sget("r_ok", (rtotal + 1) * 8);
-
-		if (!r_ck || !r_ok)
-			return fail(GG_ENOMEM, "recv scratch");
-		GG_TRY(comm_alltoallv_i64(s_ckb, offs.data(), cnts.data(),
-					  r_ck, roffs.data(), rcnts.data()));
-		GG_TRY(comm_alltoallv_i64(s_okb, offs.data(), cnts.data(),
-					  r_ok, roffs.data(), rcnts.data()));
-
-		unsigned long long nm = 0;
-		int64_t *m_ok = (int64_t *) p->sget("m_ok", (rtotal + 1) * 8);
-		int64_t *m_nat = (int64_t *) p->sget("m_pay", (rtotal + 1) * 8);
-
-		if (!m_ok || !m_nat)
-			return fail(GG_ENOMEM, "match scratch");
-		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-		GG_HIP(launch_probe_cust_map_compact(e.stream, r_ck, r_ok,
-						     (int64_t) rtotal, cust,
-						     cust_dense, cust_dlen,
-						     m_ok, m_nat, ctr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_TRY(read_counter(ctr, &nm));
-
-		std::vector<unsigned long long> cnts2(nseg), offs2(nseg + 1, 0);
-
-		GG_HIP(hipMemsetAsync(dcnt, 0, (size_t) nseg * 8, e.stream));
-		GG_HIP(launch_part_count(e.stream, m_ok, (int64_t) nm, nseg,
-					 dcnt));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		GG_HIP(hipMemcpy(cnts2.data(), dcnt, (size_t) nseg * 8,
-				 hipMemcpyDeviceToHost));
-		for (int i = 0; i < nseg; i++)
-			offs2[i + 1] = offs2[i] + cnts2[i];
-
-		int64_t *s2_ok = (int64_t *) p->sget("s2_ok", (nm + 1) * 8);
-		int64_t *s2_nat = (int64_t *) p->sget("s2_pay", (nm + 1) * 8);
-
-		if (!s2_ok || !s2_nat)
-			return fail(GG_ENOMEM, "send2 scratch");
-		GG_HIP(hipMemcpy(doffs, offs2.data(), (size_t) nseg * 8,
-				 hipMemcpyHostToDevice));
-		GG_HIP(launch_part_scatter3(e.stream, m_ok, (int64_t) nm, nseg,
-					    m_ok, m_nat, nullptr, doffs,
-					    s2_ok, s2_nat, nullptr));
-		GG_HIP(hipStreamSynchronize(e.stream));
-
-		std::vector<unsigned long long> allcnt2((size_t) nseg * nseg);
-		{
-			unsigned long long *g = (unsigned long long *)
-				p->sget("cntg", (size_t) (nseg + nseg * nseg) * 8);
-
-			GG_HIP(hipMemcpy(g, cnts2.data(), (size_t) nseg * 8,
-					 hipMemcpyHostToDevice));
-			GG_TRY(comm_allgather_u64(g, g + nseg, nseg));
-			GG_HIP(hipMemcpy(allcnt2.data(), g + nseg,
-					 allcnt2.size() * 8,
-					 hipMemcpyDeviceToHost));
-		}
-		std::vector<unsigned long long> rcnts2(nseg), roffs2(nseg + 1, 0);
-
-		for (int s2 = 0; s2 < nseg; s2++)
-			rcnts2[s2] = allcnt2[(size_t) s2 * nseg + me];
-		for (int i = 0; i < nseg; i++)
-			roffs2[i + 1] = roffs2[i] + rcnts2[i];
-		uint64_t rtotal2 = roffs2[nseg];
-
-		int64_t *r2_ok = (int64_t *) p->sget("r2_ok", (rtotal2 + 1) * 8);
-		int64_t *r2_nat = (int64_t *) p->sget("r2_pay", (rtotal2 + 1) * 8);
-
-		if (!r2_ok || !r2_nat)
-			return fail(GG_ENOMEM, "recv2 scratch");
-		GG_TRY(comm_alltoallv_i64(s2_ok, offs2.data(), cnts2.data(),
-					  r2_ok, roffs2.data(), rcnts2.data()));
-		GG_TRY(comm_alltoallv_i64(s2_nat, offs2.data(), cnts2.data(),
-					  r2_nat, roffs2.data(),
-					  rcnts2.data()));
-
-		nmatch = rtotal2;
-		if (ord_dlen)
-		{
-			GG_HIP(launch_dn_insert_orders_q5_u8(
-				e.stream, r2_ok, r2_nat, (int64_t) rtotal2,
-				ordd_pay8, ord_dlen));
-			GG_HIP(hipStreamSynchronize(e.stream));
-		}
-		else
-		{
 		if (!p->ord_slots)
 			p->ord_slots = next_pow2(2 * (rtotal2 + 1));
-		ord.nslots = p->ord_slots;
-		ord.bloom_words = ord.nslots / 8 < 1024 ? 1024 : ord.nslots / 8;
-		ord.keys = (unsigned long long *)
-			p->sget("ord.keys", ord.nslots * 8);
-		ord.payload = (unsigned long long *)
-			p->sget("ord.pay", ord.nslots * 8);
-		ord.bloom = (unsigned long long *)
-			p->sget("ord.bloom", ord.bloom_words * 8);
-		if (!ord.keys || !ord.payload || !ord.bloom)
-			return fail(GG_ENOMEM, "ord table");
-		GG_HIP(hipMemsetAsync(ord.keys, 0, ord.nslots * 8, e.stream));
-		GG_HIP(hipMemsetAsync(ord.bloom, 0, ord.bloom_words * 8,
-				      e.stream));
-		GG_HIP(launch_insert_orders(e.stream, r2_ok, r2_nat,
-					    (int64_t) rtotal2, ord));
-		GG_HIP(hipStreamSynchronize(e.stream));
-		}
-		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("orders_exchange");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += od->nrows;
-		st.rows_out += (int64_t) nmatch;
+		GG_TRY(hash_table_alloc(p, "ord", p->ord_slots,
+					HT_PAYLOAD | HT_BLOOM, &S.ord));
+		GG_HIP(launch_insert_orders(e.stream, r2[0], r2[1],
+					    (int64_t) rtotal2, S.ord));
 	}
+	GG_HIP(hipStreamSynchronize(e.stream));
+	p->stat("orders_exchange").add(tm.stop(), nrows, (int64_t) S.nmatch);
+	return GG_OK;
+}
 
-	/* 4. lineitem probe + 25-nation aggregation */
-	unsigned long long *acc = (unsigned long long *)
-		p->sget("q5acc", GG_NNATIONS * 3 * 8);
-	unsigned long long njoin = 0;
+/* EXPERIMENT (measured equal to the fused probe at
+ * SF100: 2.38 vs 2.32 ms — the compact pass's 4.8 GB
+ * stream costs what the skipped wide-column lines
+ * saved; kept behind GG_Q5_TWOPASS as evidence):
+ * compact order-matching rows into per-block
+ * regions (LDS counters, no global returning
+ * atomics), then gather the wide columns for the
+ * ~3% survivors.  *done = false on a region overflow: acc and ctr are
+ * zeroed again for the fused one-pass probe. */
+static gg_status q5_probe_twopass(Q5State &S, bool *done)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.li->nrows;
+	/* must equal the launcher's dn_grid(n) */
+	int grid = (int) ((nrows + 255) / 256);
 
-	if (!acc)
-		return fail(GG_ENOMEM, "acc");
-	GG_HIP(hipMemsetAsync(acc, 0, GG_NNATIONS * 3 * 8, e.stream));
-	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
+	if (grid > 2048)
+		grid = 2048;
+	if (grid < 1)
+		grid = 1;
+	int64_t per_block = (nrows + (int64_t) grid * 256 - 1) /
+		((int64_t) grid * 256) * 256;
+	int64_t region = per_block / 4 + 4096;
+	unsigned long long *comp = (unsigned long long *)
+		p->sget("q5.comp", (size_t) grid * region * 8);
+	unsigned long long *ccnt = (unsigned long long *)
+		p->sget("q5.ccnt", (size_t) grid * 8 + 8);
+
+	if (!comp || !ccnt)
+		return fail(GG_ENOMEM, "q5 compact");
+	unsigned long long *ovf = ccnt + grid;
+	unsigned long long hovf = 0;
+
+	GG_HIP(hipMemsetAsync(ovf, 0, 8, e.stream));
+	GG_HIP(launch_dn_q5_compact(e.stream, S.l_ok, nrows, S.ordd_pay8,
+				    S.ord_dlen, region, comp, ccnt));
+	GG_HIP(launch_dn_q5_gather(e.stream, comp, ccnt, region, grid, S.l_sk,
+				   S.l_pc, S.l_dc, S.supp_dense,
+				   S.supp_dense_len, S.acc, S.ctr, ovf));
+	GG_HIP(hipStreamSynchronize(e.stream));
+	GG_TRY(read_counter(ovf, &hovf));
+	*done = !hovf;
+	if (hovf)
 	{
-		Timed tm(e.stream);
-
-		bool twopass_done = false;
-
-		if (ord_dlen && getenv("GG_Q5_TWOPASS"))
-		{
-			/* EXPERIMENT (measured equal to the fused probe at
-			 * SF100: 2.38 vs 2.32 ms — the compact pass's 4.8 GB
-			 * stream costs what the skipped wide-column lines
-			 * saved; kept behind GG_Q5_TWOPASS as evidence):
-			 * compact order-matching rows into per-block
-			 * regions (LDS counters, no global returning
-			 * atomics), then gather the wide columns for the
-			 * ~3% survivors.  Overflow falls back to the fused
-			 * probe. */
-			/* must equal the launcher's dn_grid(n) */
-			int grid = (int) ((li->nrows + 255) / 256);
-
-			if (grid > 2048)
-				grid = 2048;
-			if (grid < 1)
-				grid = 1;
-			int64_t per_block =
-				(li->nrows + (int64_t) grid * 256 - 1) /
-				((int64_t) grid * 256) * 256;
-			int64_t region = per_block / 4 + 4096;
-			unsigned long long *comp = (unsigned long long *)
-				p->sget("q5.comp",
-					(size_t) grid * region * 8);
-			unsigned long long *ccnt = (unsigned long long *)
-				p->sget("q5.ccnt", (size_t) grid * 8 + 8);
-
-			if (!comp || !ccnt)
-				return fail(GG_ENOMEM, "q5 compact");
-			unsigned long long *ovf = ccnt + grid;
-
-			GG_HIP(hipMemsetAsync(ovf, 0, 8, e.stream));
-			GG_HIP(launch_dn_q5_compact(e.stream, l_ok,
-						    li->nrows, ordd_pay8,
-						    ord_dlen, region, comp,
-						    ccnt));
-			GG_HIP(launch_dn_q5_gather(e.stream, comp, ccnt,
-						   region, grid, l_sk, l_pc,
-						   l_dc, supp_dense,
-						   supp_dense_len, acc, ctr,
-						   ovf));
-			unsigned long long hovf = 0;
-
-			GG_HIP(hipStreamSynchronize(e.stream));
-			GG_TRY(read_counter(ovf, &hovf));
-			if (!hovf)
-				twopass_done = true;
-			else
-			{	/* region overflow: redo with the fused
-				 * one-pass probe */
-				GG_HIP(hipMemsetAsync(acc, 0,
-						      GG_NNATIONS * 3 * 8,
-						      e.stream));
-				GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
-			}
-		}
-		if (ord_dlen)
-		{
-			if (!twopass_done)
-				GG_HIP(launch_dn_probe_lineitem_q5_u8(
-					e.stream, l_ok, l_sk, l_pc, l_dc,
-					li->nrows, ordd_pay8, ord_dlen,
-					supp_dense, supp_dense_len, acc,
-					ctr));
-		}
-		else
-			GG_HIP(launch_probe_lineitem_q5(
-				e.stream, l_ok, l_sk, l_pc, l_dc, li->nrows,
-				ord, supp, supp_dense, supp_dense_len, acc,
-				ctr));
-		double ms = tm.stop();
-		GG_TRY(read_counter(ctr, &njoin));
-		KernelStatAcc &st = p->stat("probe_lineitem_q5");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += li->nrows;
-		st.rows_out += (int64_t) njoin;
-		st.hbm_bytes += li->nrows * 32;	/* okey,skey,price,disc */
+		GG_HIP(hipMemsetAsync(S.acc, 0, GG_NNATIONS * 3 * 8,
+				      e.stream));
+		GG_HIP(hipMemsetAsync(S.ctr, 0, 8, e.stream));
 	}
+	return GG_OK;
+}
 
-	/* 5. combine + finalize */
-	std::vector<unsigned long long> hacc(GG_NNATIONS * 3);
+/* 4. lineitem probe + 25-nation aggregation */
+static gg_status q5_probe_lineitem(Q5State &S)
+{
+	Engine &e = engine();
+	Pipeline *p = S.p;
+	int64_t nrows = S.li->nrows;
+	unsigned long long njoin = 0;
+	bool twopass_done = false;
 
-	GG_HIP(hipMemcpy(hacc.data(), acc, hacc.size() * 8,
-			 hipMemcpyDeviceToHost));
+	S.acc = (unsigned long long *) p->sget("q5acc", GG_NNATIONS * 3 * 8);
+	if (!S.acc)
+		return fail(GG_ENOMEM, "acc");
+	GG_HIP(hipMemsetAsync(S.acc, 0, GG_NNATIONS * 3 * 8, e.stream));
+	GG_HIP(hipMemsetAsync(S.ctr, 0, 8, e.stream));
 
+	Timed tm(e.stream);
+
+	if (S.ord_dlen && getenv("GG_Q5_TWOPASS"))
+		GG_TRY(q5_probe_twopass(S, &twopass_done));
+	if (!S.ord_dlen)
+		GG_HIP(launch_probe_lineitem_q5(
+			e.stream, S.l_ok, S.l_sk, S.l_pc, S.l_dc, nrows,
+			S.ord, S.supp, S.supp_dense, S.supp_dense_len, S.acc,
+			S.ctr));
+	else if (!twopass_done)
+		GG_HIP(launch_dn_probe_lineitem_q5_u8(
+			e.stream, S.l_ok, S.l_sk, S.l_pc, S.l_dc, nrows,
+			S.ordd_pay8, S.ord_dlen, S.supp_dense,
+			S.supp_dense_len, S.acc, S.ctr));
+	double ms = tm.stop();
+
+	GG_TRY(read_counter(S.ctr, &njoin));
+	/* okey, skey, price, disc */
+	p->stat("probe_lineitem_q5").add(ms, nrows, (int64_t) njoin,
+					 nrows * 32);
+	return GG_OK;
+}
+
+/* 5. combine + finalize */
+static gg_status q5_combine(Q5State &S, void *arena, size_t *written)
+{
+	const int nseg = engine().cfg.n_segments;
+	const size_t per = GG_NNATIONS * 3;
+	std::vector<unsigned long long> hacc(per);
 	u128 rev[GG_NNATIONS];
 	uint64_t cnt[GG_NNATIONS];
 
+	GG_HIP(hipMemcpy(hacc.data(), S.acc, per * 8, hipMemcpyDeviceToHost));
+	if (nseg > 1)
+		GG_TRY(allgather_host_u64(S.p, "q5gather", S.acc, per, hacc,
+					  hipMemcpyDeviceToDevice));
 	for (int n = 0; n < GG_NNATIONS; n++)
 	{
-		cnt[n] = hacc[n * 3];
-		rev[n] = ((u128) hacc[n * 3 + 1]) |
-			((u128) hacc[n * 3 + 2] << 64);
+		cnt[n] = 0;
+		rev[n] = 0;
 	}
-	if (nseg > 1)
-	{
-		size_t per = GG_NNATIONS * 3;
-		unsigned long long *g = (unsigned long long *)
-			p->sget("q5gather", (per + per * (size_t) nseg) * 8);
-
-		if (!g)
-			return fail(GG_ENOMEM, "q5 gather");
-		GG_HIP(hipMemcpy(g, acc, per * 8, hipMemcpyDeviceToDevice));
-		GG_TRY(comm_allgather_u64(g, g + per, per));
-		std::vector<unsigned long long> all(per * (size_t) nseg);
-
-		GG_HIP(hipMemcpy(all.data(), g + per, all.size() * 8,
-				 hipMemcpyDeviceToHost));
+	for (size_t r = 0; r < hacc.size() / per; r++)
 		for (int n = 0; n < GG_NNATIONS; n++)
 		{
-			cnt[n] = 0;
-			rev[n] = 0;
-		}
-		for (int r = 0; r < nseg; r++)
-			for (int n = 0; n < GG_NNATIONS; n++)
-			{
-				const unsigned long long *v =
-					&all[per * (size_t) r + (size_t) n * 3];
+			const unsigned long long *v =
+				&hacc[per * r + (size_t) n * 3];
 
-				cnt[n] += v[0];
-				rev[n] += ((u128) v[1]) | ((u128) v[2] << 64);
-			}
-	}
+			cnt[n] += v[0];
+			rev[n] += ((u128) v[1]) | ((u128) v[2] << 64);
+		}
 
 	std::vector<gg_q5_result_row> rows;
 
@@ -3255,6 +2881,58 @@ orders_done:;
 		    rows.size() * sizeof(gg_q5_result_row));
 	*written = sizeof(*hdr) + rows.size() * sizeof(gg_q5_result_row);
 	return GG_OK;
+}
+
+static gg_status exec_q5(Pipeline *p, void *arena, size_t bytes,
+			 size_t *written)
+{
+	Q5State S{};
+
+	S.p = p;
+	S.li = get_table(p->desc.lineitem);
+	S.od = get_table(p->desc.orders);
+	S.cu = get_table(p->desc.customer);
+	S.su = get_table(p->desc.supplier);
+	S.na = get_table(p->desc.nation);
+	S.exch = engine().cfg.n_segments > 1 ||
+		getenv("GG_FORCE_EXCHANGE") != nullptr;
+
+	if (bytes < sizeof(gg_q5_result_hdr) +
+	    GG_NNATIONS * sizeof(gg_q5_result_row))
+		return fail(GG_EINVAL, "arena too small");
+
+	S.l_ok = (const int64_t *) S.li->col("orderkey");
+	S.l_sk = (const int64_t *) S.li->col("suppkey");
+	S.l_pc = (const int64_t *) S.li->col("price");
+	S.l_dc = (const int64_t *) S.li->col("disc");
+	S.o_ok = (const int64_t *) S.od->col("orderkey");
+	S.o_ck = (const int64_t *) S.od->col("custkey");
+	S.o_dt = (const int32_t *) S.od->col("orderdate");
+	S.c_ck = (const int64_t *) S.cu->col("custkey");
+	S.c_nk = (const uint8_t *) S.cu->col("nationkey");
+	S.s_sk = (const int64_t *) S.su->col("suppkey");
+	S.s_nk = (const uint8_t *) S.su->col("nationkey");
+	S.n_nk = (const int32_t *) S.na->col("nationkey");
+	S.n_rk = (const int32_t *) S.na->col("regionkey");
+	if (!S.l_ok || !S.l_sk || !S.l_pc || !S.l_dc || !S.o_ok || !S.o_ck ||
+	    !S.o_dt || !S.c_ck || !S.c_nk || !S.s_sk || !S.s_nk || !S.n_nk ||
+	    !S.n_rk)
+		return fail(GG_EINVAL, "Q5: missing column");
+
+	S.date_lo = p->desc.cutoff_date;
+	S.date_hi = p->desc.cutoff_hi;
+	S.regionkey = p->desc.regionkey;
+	S.ctr = (unsigned long long *) p->sget("ctr", 8);
+	if (!S.ctr)
+		return fail(GG_ENOMEM, "scratch");
+
+	GG_TRY(q5_nation_dim(S));
+	GG_TRY(q5_build_customer_map(S));
+	GG_TRY(q5_build_supplier(S));
+	GG_TRY(q5_orders_layout(S));
+	GG_TRY(S.exch ? q5_orders_exchange(S) : q5_build_orders_local(S));
+	GG_TRY(q5_probe_lineitem(S));
+	return q5_combine(S, arena, written);
 }
 
 extern "C" gg_status

@@ -1,6 +1,6 @@
 /*
- * Internal engine declarations — host side (engine_abi.cpp, comm.cpp)
- * and the kernel-launcher entry points implemented in kernels.hip.
+ * Internal engine declarations — host side (engine_abi.cpp, exchange.cpp,
+ * comm.cpp) and the kernel-launcher entry points implemented in kernels.hip.
  * Product code: never includes anything from oracle/.
  */
 #ifndef GG_ENGINE_INTERNAL_H
@@ -33,6 +33,9 @@ gg_status fail(gg_status st, const char *fmt, ...);
 					  __FILE__, __LINE__, \
 					  hipGetErrorString(_e), #call); \
 	} while (0)
+
+#define GG_TRY(expr) \
+	do { gg_status _s = (expr); if (_s != GG_OK) return _s; } while (0)
 
 /* device accumulator block for Q1 (matches kernels.hip layout) */
 struct Q1DeviceAcc
@@ -137,7 +140,45 @@ struct KernelStatAcc
 	int64_t rows_in = 0;
 	int64_t rows_out = 0;
 	int64_t hbm_bytes = 0;
+
+	/* book one timed launch */
+	void add(double ms, int64_t in, int64_t out = 0, int64_t hbm = 0)
+	{
+		launches++;
+		total_ms += ms;
+		rows_in += in;
+		rows_out += out;
+		hbm_bytes += hbm;
+	}
 };
+
+/* grow-only named device scratch: the buffer `name` of at least `bytes`
+ * bytes, reallocated (contents lost) when it has to grow; nullptr when the
+ * device is out of memory */
+typedef std::vector<std::pair<std::string, std::pair<void *, size_t>>>
+	ScratchVec;
+
+inline void *scratch_get(ScratchVec &v, const char *name, size_t bytes)
+{
+	for (auto &kv : v)
+		if (kv.first == name)
+		{
+			if (kv.second.second >= bytes)
+				return kv.second.first;
+			(void) hipFree(kv.second.first);
+			kv.second.first = nullptr;
+			if (hipMalloc(&kv.second.first, bytes) != hipSuccess)
+				return nullptr;
+			kv.second.second = bytes;
+			return kv.second.first;
+		}
+	void *p = nullptr;
+
+	if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess)
+		return nullptr;
+	v.push_back({name, {p, bytes}});
+	return p;
+}
 
 /* internal pipeline kind for generic compiled plans */
 #define GG_PIPE_PLAN_INTERNAL 99
@@ -154,7 +195,7 @@ struct Pipeline
 	 * exchange buffers): avoids per-execute hipMalloc/hipFree of
 	 * hundreds of MB (ExecHashTableCreate is likewise once per
 	 * rescan in the reference, nodeHash.c:270) */
-	std::vector<std::pair<std::string, std::pair<void *, size_t>>> scratch;
+	ScratchVec scratch;
 	/* table sizings resolved on first execute (data is immutable
 	 * per pipeline), skipping the count passes afterwards */
 	uint64_t cust_slots = 0;
@@ -183,24 +224,7 @@ struct Pipeline
 
 	void *sget(const char *name, size_t bytes)
 	{
-		for (auto &kv : scratch)
-			if (kv.first == name)
-			{
-				if (kv.second.second >= bytes)
-					return kv.second.first;
-				(void) hipFree(kv.second.first);
-				kv.second.first = nullptr;
-				if (hipMalloc(&kv.second.first, bytes) != hipSuccess)
-					return nullptr;
-				kv.second.second = bytes;
-				return kv.second.first;
-			}
-		void *p = nullptr;
-
-		if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess)
-			return nullptr;
-		scratch.push_back({name, {p, bytes}});
-		return p;
+		return scratch_get(scratch, name, bytes);
 	}
 
 	/* bytes a named scratch buffer holds now (0 = none yet) */
@@ -233,29 +257,11 @@ struct Engine
 	/* engine-level grow-only device scratch (standalone ABI calls
 	 * like hash_groupby_i64: repeated calls reuse instead of
 	 * re-mapping tens of GB per call); freed at shutdown */
-	std::vector<std::pair<std::string, std::pair<void *, size_t>>> escratch;
+	ScratchVec escratch;
 
 	void *esget(const char *name, size_t bytes)
 	{
-		for (auto &kv : escratch)
-			if (kv.first == name)
-			{
-				if (kv.second.second >= bytes)
-					return kv.second.first;
-				(void) hipFree(kv.second.first);
-				kv.second.first = nullptr;
-				if (hipMalloc(&kv.second.first, bytes)
-				    != hipSuccess)
-					return nullptr;
-				kv.second.second = bytes;
-				return kv.second.first;
-			}
-		void *p = nullptr;
-
-		if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess)
-			return nullptr;
-		escratch.push_back({name, {p, bytes}});
-		return p;
+		return scratch_get(escratch, name, bytes);
 	}
 
 	/* same, for pinned host memory (hipHostMalloc is ~1 GB/s of
@@ -971,6 +977,29 @@ gg_status plan_rtc_compile(const PlanDev &D, bool has_gnull0,
 gg_status plan_rtc_launch(hipStream_t s, const std::shared_ptr<void> &h,
 			  const PlanDev &P, int grid, int block,
 			  const PlanWhereDev *W = nullptr);
+
+/* comm.cpp */
+gg_status comm_make_id(void *out_id128);
+gg_status comm_init(const void *id128);
+gg_status comm_destroy();
+bool comm_ready();
+gg_status comm_allgather_u64(const void *dev_send, void *dev_recv,
+			     size_t count);
+gg_status comm_alltoallv_i64(const int64_t *send_base,
+			     const unsigned long long *send_offs,
+			     const unsigned long long *send_cnts, int64_t *recv_base,
+			     const unsigned long long *recv_offs,
+			     const unsigned long long *recv_cnts);
+
+/* exchange.cpp */
+gg_status allgather_host_u64(Pipeline *p, const char *scratch,
+			     const unsigned long long *mine, size_t count,
+			     std::vector<unsigned long long> &all,
+			     hipMemcpyKind from = hipMemcpyHostToDevice);
+gg_status motion_redistribute(Pipeline *p, const int64_t *key,
+			      const int64_t *const in[3], int64_t n,
+			      const char *tag, int64_t *out[3],
+			      uint64_t *nrecv);
 
 /* engine_abi.cpp helpers shared with plan.cpp */
 Table *engine_table(gg_table h);

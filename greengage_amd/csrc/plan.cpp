@@ -22,13 +22,6 @@
 namespace gg
 {
 
-gg_status comm_allgather_u64(const void *dev_send, void *dev_recv,
-			     size_t count);
-bool comm_ready();
-
-#define GG_TRY(expr) \
-	do { gg_status _s = (expr); if (_s != GG_OK) return _s; } while (0)
-
 typedef __int128 i128;
 
 struct PlanResolved
@@ -876,15 +869,9 @@ plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
 	else
 		GG_HIP(launch_plan_scan_agg(e.stream, D, W));
 	if (tm)
-	{
-		double ms = tm->stop();
-		KernelStatAcc &st = p->stat("plan_scan_agg");
-
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += R->scan_rows;
-		st.hbm_bytes += R->scan_rows * R->pred_bytes_per_row;
-	}
+		p->stat("plan_scan_agg").add(tm->stop(), R->scan_rows, 0,
+					     R->scan_rows *
+					     R->pred_bytes_per_row);
 	GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
 	GG_HIP(launch_plan_compact(e.stream, D.tkeys, D.tvals, D.nslots,
 				   D.naggs, dout, ctr, D.nslots));
@@ -1017,24 +1004,22 @@ plan_group_pack(Engine &e, Pipeline *p, PlanResolved *R)
 			if (!comm_ready())
 				return fail(GG_ESTATE,
 					    "multi-segment plan without comm");
-			unsigned long long *d = (unsigned long long *)
-				p->sget("plan.gprange",
-					(4 + 4 * (size_t) nseg) * 8);
-			int64_t mine[4] = {mn[0], mx[0], mn[1], mx[1]};
-			std::vector<int64_t> all(4 * (size_t) nseg);
+			/* the ranges travel as their two's-complement words */
+			unsigned long long mine[4] = {
+				(unsigned long long) mn[0],
+				(unsigned long long) mx[0],
+				(unsigned long long) mn[1],
+				(unsigned long long) mx[1]};
+			std::vector<unsigned long long> all;
 
-			if (!d)
-				return fail(GG_ENOMEM, "plan comm scratch");
-			GG_HIP(hipMemcpy(d, mine, sizeof(mine),
-					 hipMemcpyHostToDevice));
-			GG_TRY(comm_allgather_u64(d, d + 4, 4));
-			GG_HIP(hipMemcpy(all.data(), d + 4, all.size() * 8,
-					 hipMemcpyDeviceToHost));
+			GG_TRY(allgather_host_u64(p, "plan.gprange", mine, 4,
+						  all));
 			for (int r = 0; r < nseg; r++)
 				for (int g = 0; g < 2; g++)
 				{
-					mn[g] = std::min(mn[g], all[4 * r + 2 * g]);
-					mx[g] = std::max(mx[g],
+					mn[g] = std::min(mn[g], (int64_t)
+							 all[4 * r + 2 * g]);
+					mx[g] = std::max(mx[g], (int64_t)
 							 all[4 * r + 2 * g + 1]);
 				}
 		}
@@ -1155,14 +1140,7 @@ plan_build_joins(Engine &e, Pipeline *p, PlanResolved *R,
 			}
 		}
 		GG_HIP(launch_plan_build(e.stream, B.bd));
-		{
-			double ms = tm.stop();
-			KernelStatAcc &st = p->stat("plan_build");
-
-			st.launches++;
-			st.total_ms += ms;
-			st.rows_in += B.bd.n;
-		}
+		p->stat("plan_build").add(tm.stop(), B.bd.n);
 		R->dev.joins[j].bits = B.bd.bits;
 		R->dev.joins[j].dlen = B.bd.dlen;
 		R->dev.joins[j].hkeys = B.bd.hkeys;
@@ -1360,17 +1338,10 @@ plan_combine_segments(Engine &e, Pipeline *p, const PlanResolved *R,
 		return fail(GG_ESTATE,
 			    "multi-segment plan without comm");
 	/* max group count, then padded allgather of rows */
-	std::vector<unsigned long long> cnts(nseg);
-	unsigned long long *g = (unsigned long long *)
-		p->sget("plan.cntg", (1 + (size_t) nseg) * 8);
-
-	if (!g)
-		return fail(GG_ENOMEM, "plan comm scratch");
-	GG_HIP(hipMemcpy(g, &ng, 8, hipMemcpyHostToDevice));
-	GG_TRY(comm_allgather_u64(g, g + 1, 1));
-	GG_HIP(hipMemcpy(cnts.data(), g + 1, (size_t) nseg * 8,
-			 hipMemcpyDeviceToHost));
+	std::vector<unsigned long long> cnts;
 	uint64_t mx = 0;
+
+	GG_TRY(allgather_host_u64(p, "plan.cntg", &ng, 1, cnts));
 
 	for (int r = 0; r < nseg; r++)
 		mx = std::max(mx, (uint64_t) cnts[r]);
@@ -1768,14 +1739,10 @@ plan_having_device(Engine &e, Pipeline *p, const PlanResolved *R,
 					 plan_rowsz(R), idx, ctr));
 	{
 		double ms = tm.stop();
-		KernelStatAcc &st = p->stat("plan_having");
 
 		GG_HIP(hipStreamSynchronize(e.stream));
 		GG_HIP(hipMemcpy(&ns, ctr, 8, hipMemcpyDeviceToHost));
-		st.launches++;
-		st.total_ms += ms;
-		st.rows_in += (int64_t) ng;
-		st.rows_out += (int64_t) ns;
+		p->stat("plan_having").add(ms, (int64_t) ng, (int64_t) ns);
 	}
 	if (ns > ng)
 		return fail(GG_ESTATE, "plan having overflow");
