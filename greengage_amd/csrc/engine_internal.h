@@ -16,6 +16,7 @@
 
 #include "../../include/engine_abi.h"
 #include "../../include/gg_result.h"
+#include "plan_dev.h"
 #include "plan_having.h"
 #include "q1_pack.h"
 
@@ -639,81 +640,11 @@ hipError_t launch_td_map(hipStream_t s, const uint32_t *rowslot,
 			 int64_t n, const int32_t *slot_to_id,
 			 int32_t *codes);
 
-/* ---- generic compiled plans (plan.hip / plan.cpp) ---- */
-
-struct PlanPredDev
-{
-	const void *col;
-	const uint8_t *nulls;
-	int width;
-	int64_t lo, hi;
-};
-
-struct PlanJoinDev
-{
-	const void *pkey;
-	const uint8_t *pnulls;
-	int width;
-	const unsigned long long *bits;	/* dense membership bitmap, or */
-	int64_t dlen;
-	const unsigned long long *hkeys;	/* hash semi-set (key^msb, 0=empty) */
-	uint64_t hslots;
-};
-
-/* dense index map "no build row"; INNER and LEFT build sides stay below
- * it.  It is also what a LEFT join leaves in a row's index when the row
- * has no partner (NULL-extended): the kernels test for it AHEAD of every
- * address computation, NULL-flag loads included, and never load with it */
-#define PL_NOROW 0xFFFFFFFFu
-/* bits of the plan error word (PlanDev.err) */
-#define PL_ERR_FULL 1ull	/* group table full */
-#define PL_ERR_BAKE_MISS 2ull	/* baked kernel met an unbaked code */
-#define PL_ERR_DUP_KEY 4ull	/* INNER build key not unique, INT64_MIN or
-				 * outside the dense map */
-
-/* One device accumulator slot (two u64 words).  kind 0..2 are the
- * descriptor's COUNT(*) / COUNT(factors non-NULL) / SUM; plan.cpp
- * lowers MIN, MAX and AVG onto these plus two order-encoded kinds:
- *   3 = MIN word: ~(x ^ 0x8000000000000000)   } combined by UNSIGNED
- *   4 = MAX word:   x ^ 0x8000000000000000    } max; word 1 unused
- * Zero is the identity of both, so zero-initialised tables and the
- * skip-zero flushes need no special case; the paired count slot tells
- * "no input" from a real INT64_MAX / INT64_MIN. */
-struct PlanAggDev
-{
-	int kind;		/* 0..4, see above */
-	int nf;
-	const void *col[3];
-	const uint8_t *nulls[3];
-	int width[3];
-	int8_t mod[3];		/* gg_plan_fmod */
-};
-
-/* What INNER joins add to a plan, kept in ONE block at the end of
- * PlanDev: every field a plan without an INNER join reads keeps the
- * offset it always had, so those plans' kernels stay the binaries they
- * were (the interpreted kernel reads its descriptor through scalar
- * loads in the row loop and was measurably slower on the Q1 shape when
- * the join and aggregate entries merely grew: DESIGN.md, "Inner joins
- * with payload columns").  Sources: 0 = the driving
- * table, 1+k = the build table of INNER or LEFT join k.  A LEFT join is
- * built and laid out as an INNER one, an ANTI join as a SEMI one; jkind
- * tells the probe what to do with the answer. */
-struct PlanPayloadDev
-{
-	/* INNER / LEFT join j: key -> build-row-index map instead of a membership
-	 * set (joins[j].bits stays NULL).  joins[j].dlen > 0: dense,
-	 * jidx[j][key], PL_NOROW = absent; else jidx[j][] runs parallel to
-	 * joins[j].hkeys[], written only where a key was installed */
-	const uint32_t *jidx[GG_PLAN_MAX_JOINS];
-	int8_t jkind[GG_PLAN_MAX_JOINS];	/* gg_plan_joinkind */
-	int8_t jpsrc[GG_PLAN_MAX_JOINS];	/* source of joins[j].pkey */
-	int8_t gsrc[2];				/* source of gcol[g] */
-	int8_t asrc[GG_PLAN_MAX_AGGS][3];	/* source of aggs[a].col[f] */
-};
+/* ---- generic compiled plans (plan.hip / plan.cpp); the device structs,
+ * sentinels and error bits are plan_dev.h's ---- */
 
 /* The two things host code asks of a gg_plan_joinkind (held as int or
- * int8_t in the structs above).  What a kind BUILDS: INNER and LEFT a
+ * int8_t in plan_dev.h's structs).  What a kind BUILDS: INNER and LEFT a
  * key -> build-row-index map, so they are column sources and the row
  * carries their index; SEMI and ANTI a membership set.  What its probe
  * DOES with a row that has no partner: LEFT keeps it (NULL-extended), and
@@ -729,95 +660,10 @@ constexpr bool gg_join_keeps_unmatched(int kind)
 	return kind == GG_JOIN_LEFT || kind == GG_JOIN_ANTI;
 }
 
-/* Packed two-column group code (engine_abi.h gg_plan_desc.group_cols):
- * code = (e0 << shift) | e1, e_g = 0 for NULL, else v - gmin[g] + 1.
- * Set for every ngroup == 2 plan but the (char1, char1) pair, which
- * keeps e0 * 512 + e1; filled at the plan's first execute, when the
- * column ranges are resolved.  Appended after `pl` for the reason given
- * there: no field of today's plans moves. */
-struct PlanGroupPackDev
-{
-	int packed;
-	int shift;		/* b1, the width of e1 */
-	int64_t gmin[2];
-};
-
-/* Aggregate filters (engine_abi.h gg_plan_filter), appended after `gp`
- * under the rule given at PlanPayloadDev: no field an existing plan reads
- * may move, so a plan without a referenced filter keeps its kernels.
- * Filter k keeps its descriptor index; `used` has bit k set iff some
- * accumulator slot references it (only those are evaluated, once per
- * row), afilt[a] is slot a's filter, 0 = none, 1+k = filter k.  A helper
- * count slot carries its aggregate's filter.  The generated kernels read
- * the block in place (P.fl; it is part of their argument bytes only when
- * `used` is non-zero); the interpreted kernel gets a copy as an argument
- * of its own (plan.hip PlFilters). */
-struct PlanFilterDev
-{
-	PlanPredDev preds[GG_PLAN_MAX_FILTERS][GG_PLAN_MAX_FILTER_PREDS];
-	int8_t psrc[GG_PLAN_MAX_FILTERS][GG_PLAN_MAX_FILTER_PREDS];
-	int8_t npreds[GG_PLAN_MAX_FILTERS];
-	int8_t afilt[GG_PLAN_MAX_AGGS];
-	int used;		/* bit k: filter k is referenced */
-};
-
-struct PlanDev
-{
-	int64_t n;
-	int npreds, njoins, naggs, ngroup;
-	PlanPredDev preds[GG_PLAN_MAX_PREDS];
-	PlanJoinDev joins[GG_PLAN_MAX_JOINS];
-	const void *gcol[2];
-	const uint8_t *gnulls[2];
-	int gwidth[2];
-	unsigned long long *tkeys;	/* nslots; INT64_MIN pattern = empty */
-	unsigned long long *tvals;	/* nslots * naggs * 2 (lo, hi) */
-	uint64_t nslots;
-	unsigned long long *err;
-	PlanAggDev aggs[GG_PLAN_MAX_AGGS];
-	PlanPayloadDev pl;
-	PlanGroupPackDev gp;
-	PlanFilterDev fl;
-};
-
+/* what the trailing blocks of PlanDev (plan_dev.h PLAN_DEV_TAIL) rely on */
 static_assert(offsetof(PlanDev, fl) ==
 	      offsetof(PlanDev, gp) + sizeof(PlanGroupPackDev),
 	      "PlanFilterDev follows PlanGroupPackDev without padding");
-
-/* General WHERE clauses (engine_abi.h gg_plan_where), lowered: the atoms of
- * one scope, clause after clause; clause c owns natoms[c] consecutive atoms.
- * For scope 0 the first nscan clauses read the driving table alone (scan
- * clauses, evaluated with the scan preds ahead of the joins), the others
- * read some payload column (post-join clauses, evaluated once per row that
- * survived preds and joins, ahead of the aggregate filters and the group
- * code).  A build scope holds scan clauses only.
- *
- * The block is NOT a member of PlanDev.  The rule given at PlanPayloadDev
- * (no field an existing plan reads may move) would allow appending it, but
- * the interpreted kernel already carries PlanDev plus a PlFilters copy in
- * its kernarg segment and a member here would be a third copy past the
- * 4 KiB a launch may pass.  It reaches the interpreted kernel as an argument
- * of its own (plan.hip PlWhere), the generated kernels as a trailing block
- * directly behind PlanDev's bytes (plan_rtc.cpp GP_MEMBER), and k_plan_build
- * as the last member of PlanBuildDev. */
-struct PlanAtomDev
-{
-	const void *col, *col2;			/* a, b (comparisons only) */
-	const uint8_t *nulls, *nulls2;
-	int64_t lo, hi;
-	int8_t kind;				/* gg_plan_atomkind */
-	int8_t src, src2;			/* column sources */
-	int8_t width, width2;
-};
-
-struct PlanWhereDev
-{
-	PlanAtomDev atoms[GG_PLAN_MAX_WHERE_ATOMS];
-	int8_t natoms[GG_PLAN_MAX_CLAUSES];
-	int8_t nclauses;
-	int8_t nscan;
-};
-
 static_assert(sizeof(PlanWhereDev) % 8 == 0 && alignof(PlanWhereDev) == 8,
 	      "PlanWhereDev follows PlanDev's bytes without padding");
 

@@ -52,7 +52,7 @@ struct PlanResolved
 	std::shared_ptr<void> rtc_baked;
 	bool bake_tried = false;
 	/* descriptor aggregates in order, lowered onto the device
-	 * accumulator slots dev.aggs[] (engine_internal.h PlanAggDev):
+	 * accumulator slots dev.aggs[] (plan_dev.h PlanAggDev):
 	 * MIN/MAX = encoded value word + non-NULL count, AVG = SUM +
 	 * count; the helper counts are shared between aggregates over
 	 * the same factor columns */
@@ -837,14 +837,13 @@ static uint64_t next_pow2_pl(uint64_t v)
 
 /* nslots for the generic group table: supports up to ~nslots/2 groups */
 static constexpr uint64_t PL_NSLOTS = 1ull << 18;
-static constexpr unsigned long long PL_EMPTY_HOST = 0x8000000000000000ull;
 
 /* empty the group table and zero the accumulators; the error word is
  * exec_plan's, which clears it ahead of the join builds */
 static gg_status
 plan_reset_table(hipStream_t s, const PlanDev &D)
 {
-	GG_HIP(launch_fill_u64(s, D.tkeys, D.nslots, PL_EMPTY_HOST));
+	GG_HIP(launch_fill_u64(s, D.tkeys, D.nslots, PL_EMPTY));
 	GG_HIP(hipMemsetAsync(D.tvals, 0, D.nslots * (size_t) D.naggs * 16,
 			      s));
 	return GG_OK;

@@ -23,7 +23,7 @@
  *                 NULL inputs, COUNT(*) does not; MIN/MAX words
  *                 (int8smaller/int8larger) are order-encoded so both
  *                 combine by unsigned max with 0 as identity
- *                 (engine_internal.h PlanAggDev)
+ *                 (plan_dev.h PlanAggDev)
  *   agg filters   agg(...) FILTER (WHERE ...), the Aggref.aggfilter that
  *                 advance_aggregates (nodeAgg.c) evaluates ahead of the
  *                 strict transition: per-aggregate range conjunctions
@@ -309,7 +309,7 @@ void k_plan_build(PlanBuildDev B)
 			else
 			{
 				unsigned long long t = (unsigned long long) k
-					^ 0x8000000000000000ull;
+					^ PL_MSB;
 				uint64_t pos = (uint64_t) gg_hashint8(k) &
 					(B.hslots - 1);
 
@@ -390,7 +390,7 @@ pl_joins_pass(const PlanJoinDev *joins, int njoins, int64_t i)
 			else
 			{
 				unsigned long long t = (unsigned long long) k
-					^ 0x8000000000000000ull;
+					^ PL_MSB;
 				uint64_t pos = (uint64_t) gg_hashint8(k) &
 					(J.hslots - 1);
 				bool hit = false;
@@ -570,7 +570,7 @@ pl_joins_index(const PlanDev &P, int64_t i, PlRow<1> &R)
 		else if (inner)
 		{
 			unsigned long long t = (unsigned long long) k
-				^ 0x8000000000000000ull;
+				^ PL_MSB;
 			uint64_t pos = (uint64_t) gg_hashint8(k) &
 				(J.hslots - 1);
 
@@ -599,7 +599,7 @@ pl_joins_index(const PlanDev &P, int64_t i, PlRow<1> &R)
 		{
 			/* SEMI hash set, probed as pl_joins_pass does */
 			unsigned long long t = (unsigned long long) k
-				^ 0x8000000000000000ull;
+				^ PL_MSB;
 			uint64_t pos = (uint64_t) gg_hashint8(k) &
 				(J.hslots - 1);
 
@@ -678,7 +678,7 @@ pl_joins_outer(const PlanDev &P, int64_t i, PlRow<2> &R)
 					 * keeps the order pl_joins_pass has */
 					const unsigned long long t =
 						(unsigned long long) k ^
-						0x8000000000000000ull;
+						PL_MSB;
 					uint64_t pos = (uint64_t) gg_hashint8(k) &
 						(J.hslots - 1);
 					const bool semi = kind == GG_JOIN_SEMI;
@@ -822,7 +822,7 @@ pl_agg_val(const PlanAggDev &a, const int8_t *src, int64_t i,
 					 * AFTER the modifier */
 		{
 			unsigned long long e = (unsigned long long) v ^
-				0x8000000000000000ull;
+				PL_MSB;
 
 			v = (__int128) (a.kind == 3 ? ~e : e);
 		}
@@ -887,61 +887,6 @@ pl_row_filters(const PlanFilterDev &F, int64_t i, const PlRow<PL> &R)
 			fm |= 1u << k;
 	}
 	return fm;
-}
-
-static constexpr unsigned long long PL_EMPTY = 0x8000000000000000ull;
-
-/* group-table find-or-create (execHHashagg.c:905); -1 = table full */
-__device__ static inline int64_t
-pl_slot(const PlanDev &P, long long code)
-{
-	uint64_t pos = (uint64_t) gg_hashint8(code) & (P.nslots - 1);
-
-	for (uint64_t it = 0; it < P.nslots; it++)
-	{
-		unsigned long long cur = P.tkeys[pos];
-
-		if (cur == (unsigned long long) code)
-			return (int64_t) pos;
-		if (cur == PL_EMPTY)
-		{
-			unsigned long long prev =
-				atomicCAS(&P.tkeys[pos], PL_EMPTY,
-					  (unsigned long long) code);
-
-			if (prev == PL_EMPTY ||
-			    prev == (unsigned long long) code)
-				return (int64_t) pos;
-			continue;
-		}
-		pos = (pos + 1) & (P.nslots - 1);
-	}
-	return -1;
-}
-
-/* exact two-word add into registers */
-__device__ static inline void
-pl_add128(unsigned long long &lo, unsigned long long &hi,
-	  unsigned long long vlo, unsigned long long vhi)
-{
-	unsigned long long old = lo;
-
-	lo += vlo;
-	hi += vhi + (lo < old);
-}
-
-/* ... and into an accumulator w[0..1] in LDS or global memory; the
- * carry comes from the returned old low word */
-__device__ static inline void
-pl_atomic_add128(unsigned long long *w, unsigned long long vlo,
-		 unsigned long long vhi)
-{
-	unsigned long long old = atomicAdd(w, vlo);
-
-	if (old + vlo < old)
-		vhi++;
-	if (vhi)
-		atomicAdd(w + 1, vhi);
 }
 
 /* one row's transitions: every aggregate's value into its two-word
@@ -1111,7 +1056,7 @@ void k_plan_scan_agg(PlanDev P, PlFilters<FL> F, Where... W)
 	constexpr int LREPL = 8;	/* replicas split the per-word LDS
 					 * atomic serialization 8 ways (the
 					 * k_q1_agg replica pattern) */
-	constexpr long long LEMPTY = (long long) 0x8000000000000000ull;
+	constexpr long long LEMPTY = (long long) PL_EMPTY;
 	__shared__ long long lkeys[LSLOTS];
 	__shared__ unsigned long long
 		lvals[LREPL][LSLOTS][2 * GG_PLAN_MAX_AGGS];

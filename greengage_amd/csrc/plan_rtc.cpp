@@ -42,109 +42,16 @@ struct PlanRtc
 	}
 };
 
-/* device-side struct definitions, embedded verbatim so the generated
- * source sees the exact layouts engine_internal.h defines (guarded by
- * a sizeof static_assert).  GP_STRUCT / GP_MEMBER are defined by
- * emit_prelude: the trailing PlanGroupPackDev block exists only in the
- * program of a plan with a packed pair of group columns, so every other
- * plan's kernel keeps the argument block, and with it the binary, it
- * always had (plan_rtc_launch passes that many bytes).  A plan that
- * references an aggregate filter gets both trailing blocks, `gp` and the
- * PlanFilterDev after it, through the same two macros, so this text and
- * with it every other plan's program stays byte for byte what it was.  A
- * plan with scope-0 WHERE clauses gets a third block, PlanWhereDev `wh`,
- * behind those two: it is no member of the host's PlanDev (see there), the
- * launch lays it directly behind PlanDev's bytes */
-static const char *STRUCT_DEFS = R"GG(
-typedef long long int64_t;
-typedef unsigned long long uint64_t;
-typedef unsigned int uint32_t;
-typedef int int32_t;
-typedef unsigned char uint8_t;
-typedef signed char int8_t;
-
-struct PlanPredDev
-{
-	const void *col;
-	const uint8_t *nulls;
-	int width;
-	int64_t lo, hi;
-};
-
-struct PlanJoinDev
-{
-	const void *pkey;
-	const uint8_t *pnulls;
-	int width;
-	const unsigned long long *bits;
-	int64_t dlen;
-	const unsigned long long *hkeys;
-	uint64_t hslots;
-};
-
-struct PlanAggDev
-{
-	int kind;
-	int nf;
-	const void *col[3];
-	const uint8_t *nulls[3];
-	int width[3];
-	int8_t mod[3];
-};
-
-struct PlanPayloadDev
-{
-	const uint32_t *jidx[2];
-	int8_t jkind[2];
-	int8_t jpsrc[2];
-	int8_t gsrc[2];
-	int8_t asrc[8][3];
-};
-
-GP_STRUCT
-struct PlanDev
-{
-	int64_t n;
-	int npreds, njoins, naggs, ngroup;
-	PlanPredDev preds[8];
-	PlanJoinDev joins[2];
-	const void *gcol[2];
-	const uint8_t *gnulls[2];
-	int gwidth[2];
-	unsigned long long *tkeys;
-	unsigned long long *tvals;
-	uint64_t nslots;
-	unsigned long long *err;
-	PlanAggDev aggs[8];
-	PlanPayloadDev pl;
-GP_MEMBER};
-
-/* reference hashint8 (hashfunc.c:52 -> hash_any 32-bit path) */
-__device__ inline uint32_t gg_hash_uint32(uint32_t k)
-{
-	uint32_t a = 0x9e3779b9u + 4 + 3923095u;
-	uint32_t b = a, c = a;
-
-	a += k;
-	c ^= b; c -= ((b << 14) | (b >> 18));
-	a ^= c; a -= ((c << 11) | (c >> 21));
-	b ^= a; b -= ((a << 25) | (a >> 7));
-	c ^= b; c -= ((b << 16) | (b >> 16));
-	a ^= c; a -= ((c << 4) | (c >> 28));
-	b ^= a; b -= ((a << 14) | (a >> 18));
-	c ^= b; c -= ((b << 24) | (b >> 8));
-	return c;
-}
-
-__device__ inline uint32_t gg_hashint8(int64_t v)
-{
-	uint32_t lohalf = (uint32_t) v;
-	uint32_t hihalf = (uint32_t) ((uint64_t) v >> 32);
-
-	lohalf ^= (v >= 0) ? hihalf : ~hihalf;
-	return gg_hash_uint32(lohalf);
-}
-)GG";
+/* The head of every generated program: the text of gg_pg_hash.h and of
+ * plan_dev.h (the Makefile writes both into one raw string literal).  The
+ * program so sees the very structs, sentinels, hash and accumulator
+ * functions the host and plan.hip compile, not a copy of them.  It is
+ * concatenated, not passed as a hipRTC header, so a GG_PLAN_RTC_DUMP file
+ * is a whole program.  emit_prelude puts the #defines the text expects
+ * ahead of it. */
+static const char PLAN_DEV_SRC[] =
+#include "plan_dev_src.inc"
+	;
 
 /* emit a typed, width-baked load; nt = nontemporal streaming load
  * (k_q1_agg measured +11% from NT on its scan columns — the data is
@@ -181,69 +88,20 @@ static std::string fmt(const char *f, ...)
 	return buf;
 }
 
-/* device helpers every generated kernel shares; the host emitters below
- * emit CALLS to these, one per accumulator, never their bodies.  All
- * are inlined, so an LDS destination still gets ds_* atomics. */
+/* device helpers only generated kernels use (the group table and the
+ * two-word adds are plan_dev.h's); the host emitters below emit CALLS to
+ * these, one per accumulator, never their bodies.  All are inlined, so an
+ * LDS destination still gets ds_* atomics. */
 static const char *DEVICE_FNS = R"GG(
 #define LSLOTS 32
-#define LEMPTY ((long long) 0x8000000000000000ull)
+#define LEMPTY ((long long) PL_EMPTY)
 
-/* group-table find-or-create (execHHashagg.c:905); -1 = table full */
-__device__ inline int64_t gg_slot(const PlanDev &P, long long code)
-{
-	uint64_t pos = (uint64_t) gg_hashint8(code) & (P.nslots - 1);
-
-	for (uint64_t it = 0; it < P.nslots; it++)
-	{
-		unsigned long long cur = P.tkeys[pos];
-
-		if (cur == (unsigned long long) code)
-			return (int64_t) pos;
-		if (cur == 0x8000000000000000ull)
-		{
-			unsigned long long prev = atomicCAS(
-				&P.tkeys[pos], 0x8000000000000000ull,
-				(unsigned long long) code);
-
-			if (prev == 0x8000000000000000ull ||
-			    prev == (unsigned long long) code)
-				return (int64_t) pos;
-			continue;
-		}
-		pos = (pos + 1) & (P.nslots - 1);
-	}
-	return -1;
-}
-
-/* register accumulators: exact two-word add, and the unsigned max that
- * combines order-encoded MIN/MAX words (0 = identity = "no input") */
-__device__ inline void gg_add2(unsigned long long &lo, unsigned long long &hi,
-			       unsigned long long vlo, unsigned long long vhi)
-{
-	unsigned long long old = lo;
-
-	lo += vlo;
-	hi += vhi + (lo < old);
-}
-
+/* register accumulators: the unsigned max that combines order-encoded
+ * MIN/MAX words (0 = identity = "no input") */
 __device__ inline void gg_max(unsigned long long &m, unsigned long long v)
 {
 	if (v > m)
 		m = v;
-}
-
-/* two-word add into an accumulator w[0..1] in LDS or global memory; the
- * carry comes from the RETURNED old low word */
-__device__ inline void gg_atomic_add2(unsigned long long *w,
-				      unsigned long long vlo,
-				      unsigned long long vhi)
-{
-	unsigned long long old = atomicAdd(w, vlo);
-
-	if (old + vlo < old)
-		vhi++;
-	if (vhi)
-		atomicAdd(w + 1, vhi);
 }
 
 /* global-group epilogue: wave-reduce a register accumulator, one global
@@ -253,10 +111,10 @@ __device__ inline void gg_wave_flush_add(unsigned long long *dst,
 					 unsigned long long hi)
 {
 	for (int off = 32; off; off >>= 1)
-		gg_add2(lo, hi, __shfl_down(lo, off, 64),
+		pl_add128(lo, hi, __shfl_down(lo, off, 64),
 			__shfl_down(hi, off, 64));
 	if ((threadIdx.x & 63) == 0 && (lo || hi))
-		gg_atomic_add2(dst, lo, hi);
+		pl_atomic_add128(dst, lo, hi);
 }
 
 __device__ inline void gg_wave_flush_max(unsigned long long *dst,
@@ -283,9 +141,9 @@ __device__ inline void gg_wave_flush_max(unsigned long long *dst,
 			if (LW == 1) \
 				lo += (w0); \
 			else \
-				gg_add2(lo, hi, (w0), (&(w0))[1]); \
+				pl_add128(lo, hi, (w0), (&(w0))[1]); \
 		if (lo || hi) \
-			gg_atomic_add2((dst), lo, hi); \
+			pl_atomic_add128((dst), lo, hi); \
 	} while (0)
 
 #define GG_FOLD_FLUSH_MAX(dst, w0) \
@@ -329,7 +187,7 @@ static bool where_post(const Gen &G)
 	return G.W && G.W->nclauses > G.W->nscan;
 }
 
-/* Source `src` is a LEFT join.  Its index r<j> is 0xFFFFFFFF on a row the
+/* Source `src` is a LEFT join.  Its index r<j> is PL_NOROW on a row the
  * join NULL-extended, and no load may be issued with it: the row carries
  * one `bool h<j>` ("has a partner"), set once where the join is probed,
  * and every use of a column of that source tests it ahead of the address
@@ -379,85 +237,53 @@ static std::string ix_of(int src)
 	return src ? fmt("r%d", src - 1) : std::string("i");
 }
 
-/* layout guards, tunables and the device helpers */
+/* the tail level (plan_dev.h PLAN_DEV_TAIL) of a plan's program */
+static int plan_dev_tail(const PlanDev &D, const PlanWhereDev *W)
+{
+	return W ? 3 : filter_args(D) ? 2 : packed_args(D) ? 1 : 0;
+}
+
+/* the shared header behind its #defines, layout guards, tunables and the
+ * device helpers */
 static void emit_prelude(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
+	const int tail = plan_dev_tail(D, G.W);
+	/* host clang and the amdgcn compiler must agree on every struct the
+	 * program's PlanDev holds; `tail` = the lowest level that holds it */
+#define GG_LAYOUT(T, tail) {#T, sizeof(T), tail}
+	static const struct
+	{
+		const char *name;
+		size_t size;
+		int tail;
+	} layout[] = {
+		GG_LAYOUT(PlanPredDev, 0), GG_LAYOUT(PlanJoinDev, 0),
+		GG_LAYOUT(PlanAggDev, 0), GG_LAYOUT(PlanPayloadDev, 0),
+		GG_LAYOUT(PlanGroupPackDev, 1), GG_LAYOUT(PlanFilterDev, 2),
+		GG_LAYOUT(PlanAtomDev, 3), GG_LAYOUT(PlanWhereDev, 3)};
+#undef GG_LAYOUT
 
-	s += G.W
-		? "#define GP_STRUCT struct PlanGroupPackDev "
-		  "{ int packed; int shift; int64_t gmin[2]; }; "
-		  "struct PlanFilterDev { PlanPredDev preds[4][4]; "
-		  "int8_t psrc[4][4]; int8_t npreds[4]; int8_t afilt[8]; "
-		  "int used; }; "
-		  "struct PlanAtomDev { const void *col, *col2; "
-		  "const uint8_t *nulls, *nulls2; int64_t lo, hi; int8_t kind; "
-		  "int8_t src, src2; int8_t width, width2; }; "
-		  "struct PlanWhereDev { PlanAtomDev atoms[16]; "
-		  "int8_t natoms[8]; int8_t nclauses; int8_t nscan; };\n"
-		  "#define GP_MEMBER PlanGroupPackDev gp; PlanFilterDev fl; "
-		  "PlanWhereDev wh;\n"
-		: filter_args(D)
-		? "#define GP_STRUCT struct PlanGroupPackDev "
-		  "{ int packed; int shift; int64_t gmin[2]; }; "
-		  "struct PlanFilterDev { PlanPredDev preds[4][4]; "
-		  "int8_t psrc[4][4]; int8_t npreds[4]; int8_t afilt[8]; "
-		  "int used; };\n"
-		  "#define GP_MEMBER PlanGroupPackDev gp; PlanFilterDev fl;\n"
-		: packed_args(D)
-		? "#define GP_STRUCT struct PlanGroupPackDev "
-		  "{ int packed; int shift; int64_t gmin[2]; };\n"
-		  "#define GP_MEMBER PlanGroupPackDev gp;\n"
-		: "#define GP_STRUCT\n#define GP_MEMBER\n";
-	s += STRUCT_DEFS;
-	/* the struct text above is a hand copy of engine_internal.h: pin
-	 * every size and the offsets the kernels rely on */
-	s += fmt("static_assert(sizeof(PlanPredDev) == %zu, \"layout\");\n"
-		 "static_assert(sizeof(PlanJoinDev) == %zu, \"layout\");\n"
-		 "static_assert(sizeof(PlanAggDev) == %zu, \"layout\");\n"
-		 "static_assert(sizeof(PlanDev) == %zu, \"layout\");\n",
-		 sizeof(PlanPredDev), sizeof(PlanJoinDev), sizeof(PlanAggDev),
+	/* no header can be included under hipRTC: engine_abi.h's bounds go in
+	 * as the host compiled them */
+#define GG_DEF(M) s += fmt("#define " #M " %d\n", (int) M)
+	GG_DEF(GG_PLAN_MAX_PREDS);
+	GG_DEF(GG_PLAN_MAX_JOINS);
+	GG_DEF(GG_PLAN_MAX_AGGS);
+	GG_DEF(GG_PLAN_MAX_FILTERS);
+	GG_DEF(GG_PLAN_MAX_FILTER_PREDS);
+	GG_DEF(GG_PLAN_MAX_WHERE_ATOMS);
+	GG_DEF(GG_PLAN_MAX_CLAUSES);
+#undef GG_DEF
+	s += fmt("#define PLAN_DEV_TAIL %d\n", tail);
+	s += PLAN_DEV_SRC;
+	s += "using namespace gg;\n";
+	for (const auto &l : layout)
+		if (l.tail <= tail)
+			s += fmt("static_assert(sizeof(%s) == %zu, \"layout\");\n",
+				 l.name, l.size);
+	s += fmt("static_assert(sizeof(PlanDev) == %zu, \"layout\");\n",
 		 plan_arg_bytes(D, G.W));
-	s += fmt("static_assert(__builtin_offsetof(PlanDev, joins) == %zu, \"layout\");\n"
-		 "static_assert(__builtin_offsetof(PlanDev, tkeys) == %zu, \"layout\");\n"
-		 "static_assert(__builtin_offsetof(PlanDev, err) == %zu, \"layout\");\n"
-		 "static_assert(__builtin_offsetof(PlanDev, aggs) == %zu, \"layout\");\n",
-		 offsetof(PlanDev, joins), offsetof(PlanDev, tkeys),
-		 offsetof(PlanDev, err), offsetof(PlanDev, aggs));
-	s += fmt("static_assert(sizeof(PlanPayloadDev) == %zu, \"layout\");\n"
-		 "static_assert(__builtin_offsetof(PlanDev, pl) == %zu, \"layout\");\n"
-		 "static_assert(__builtin_offsetof(PlanPayloadDev, jkind) == %zu, \"layout\");\n"
-		 "static_assert(__builtin_offsetof(PlanPayloadDev, asrc) == %zu, \"layout\");\n",
-		 sizeof(PlanPayloadDev), offsetof(PlanDev, pl),
-		 offsetof(PlanPayloadDev, jkind),
-		 offsetof(PlanPayloadDev, asrc));
-	if (packed_args(D) || filter_args(D) || G.W)
-		s += fmt("static_assert(sizeof(PlanGroupPackDev) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanDev, gp) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanGroupPackDev, gmin) == %zu, \"layout\");\n",
-			 sizeof(PlanGroupPackDev), offsetof(PlanDev, gp),
-			 offsetof(PlanGroupPackDev, gmin));
-	if (G.W)
-		s += fmt("static_assert(sizeof(PlanAtomDev) == %zu, \"layout\");\n"
-			 "static_assert(sizeof(PlanWhereDev) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanDev, wh) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanAtomDev, lo) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanAtomDev, kind) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanWhereDev, natoms) == %zu, \"layout\");\n",
-			 sizeof(PlanAtomDev), sizeof(PlanWhereDev),
-			 offsetof(PlanDevWhere, wh), offsetof(PlanAtomDev, lo),
-			 offsetof(PlanAtomDev, kind),
-			 offsetof(PlanWhereDev, natoms));
-	if (filter_args(D) || G.W)
-		s += fmt("static_assert(sizeof(PlanFilterDev) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanDev, fl) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanFilterDev, psrc) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanFilterDev, afilt) == %zu, \"layout\");\n"
-			 "static_assert(__builtin_offsetof(PlanFilterDev, used) == %zu, \"layout\");\n",
-			 sizeof(PlanFilterDev), offsetof(PlanDev, fl),
-			 offsetof(PlanFilterDev, psrc),
-			 offsetof(PlanFilterDev, afilt),
-			 offsetof(PlanFilterDev, used));
 
 	/* baked variant: more replicas by default — the accumulator
 	 * array has only nbake slots, so per-word contention is higher
@@ -526,7 +352,7 @@ static void emit_hash_probe(std::string &s, const std::string &k,
 	const std::string m = "\t\t\t\tif (cur == t) " + hit + "\n";
 
 	s += "\t\t{\n\t\t\tunsigned long long t = (unsigned long long) " + k +
-		" ^ 0x8000000000000000ull;\n\t\t\tuint64_t pos = (uint64_t) "
+		" ^ PL_MSB;\n\t\t\tuint64_t pos = (uint64_t) "
 		"gg_hashint8(" + k + ") & (" + J + ".hslots - 1);\n"
 		"\t\t\tfor (;;) {\n\t\t\t\tunsigned long long cur = " + J +
 		".hkeys[pos];\n" + (empty_first ? e + m : m + e) +
@@ -552,7 +378,7 @@ static void emit_join(std::string &s, const PlanDev &D, int j)
 		nf = D.joins[j].pnulls ? J + ".pnulls[" + pi + "]" : "";
 
 	if (kind == GG_JOIN_LEFT)
-		s += "\t\t" + r + " = 0xFFFFFFFFu;\n";
+		s += "\t\t" + r + " = PL_NOROW;\n";
 	if (!keep)
 		s += (hs.empty() ? "" : "\t\tif (!" + hs + ") " + no + "\n") +
 			(nf.empty() ? "" : "\t\tif (" + nf + ") " + no + "\n");
@@ -566,10 +392,10 @@ static void emit_join(std::string &s, const PlanDev &D, int j)
 		pi.c_str());
 	if (map && D.joins[j].dlen)
 		/* dense index map: the range check comes before the map is
-		 * touched; 0xFFFFFFFF = no build row, LEFT's "no partner" */
+		 * touched; PL_NOROW = no build row, LEFT's "no partner" */
 		s += keep ? "\t\tif (" + in + ")\n\t\t\t" + take + "[" + k + "];\n"
 			: "\t\tif (" + out + ")\n\t\t\t" + no + "\n\t\t" + take + "[" +
-			  k + "];\n\t\tif (" + r + " == 0xFFFFFFFFu) " + no + "\n";
+			  k + "];\n\t\tif (" + r + " == PL_NOROW) " + no + "\n";
 	else if (!map && D.joins[j].bits)
 		/* SEMI drops a non-member; ANTI is the same test, inverted */
 		s += "\t\tif (" + (keep ? in + " &&" : out + " ||") + "\n\t\t    " +
@@ -590,7 +416,7 @@ static void emit_join(std::string &s, const PlanDev &D, int j)
 	if (kind == GG_JOIN_LEFT)
 		/* close the probe, then the row's one "has a partner" flag */
 		s += "\t\t}\n\t\th" + std::to_string(j) + " = " + r +
-			" != 0xFFFFFFFFu;\n";
+			" != PL_NOROW;\n";
 	else if (keep)
 		s += "\t\t}\n";
 }
@@ -941,7 +767,7 @@ static void emit_agg_vals(std::string &s, const Gen &G)
 			 * unsigned max combines both (MAX: x ^ msb, MIN:
 			 * its complement; 0 = identity = "no input") */
 			s += fmt("\t\tav[%d] = (VAT) %s((unsigned long long) %s"
-				 " ^ 0x8000000000000000ull);\n",
+				 " ^ PL_MSB);\n",
 				 a, D.aggs[a].kind == 3 ? "~" : "",
 				 term_of(a, 0).c_str());
 		else
@@ -1092,11 +918,11 @@ static void emit_transitions(std::string &s, const Gen &G, const char *ind,
 		else if (dest == DEST_BAKED && G.fast)
 			call = fmt("atomicAdd(&%s, %s)", w.c_str(), v.c_str());
 		else if (dest == DEST_REG)
-			call = fmt("gg_add2(%s, ahi[%d], %s, "
+			call = fmt("pl_add128(%s, ahi[%d], %s, "
 				   "(unsigned long long) (av[%d] >> 64))",
 				   w.c_str(), a, v.c_str(), a);
 		else
-			call = fmt("gg_atomic_add2(&%s, %s, "
+			call = fmt("pl_atomic_add128(&%s, %s, "
 				   "(unsigned long long) (av[%d] >> 64))",
 				   w.c_str(), v.c_str(), a);
 		s += fmt("%sif (AOK(%d))\n%s\t%s;\n", ind, a, ind,
@@ -1180,9 +1006,9 @@ static void emit_body_grouped(std::string &s, const Gen &G)
 	s += R"GG(		}
 		else
 		{
-			int64_t slot = gg_slot(P, code);
+			int64_t slot = pl_slot(P, code);
 
-			if (slot < 0) { atomicOr(P.err, 1ull); continue; }
+			if (slot < 0) { atomicOr(P.err, PL_ERR_FULL); continue; }
 )GG";
 	emit_transitions(s, G, "\t\t\t", DEST_GLOBAL);
 	s += R"GG(		}
@@ -1192,9 +1018,9 @@ static void emit_body_grouped(std::string &s, const Gen &G)
 	{
 		if (lkeys[q] == LEMPTY)
 			continue;
-		int64_t slot = gg_slot(P, lkeys[q]);
+		int64_t slot = pl_slot(P, lkeys[q]);
 
-		if (slot < 0) { atomicOr(P.err, 1ull); continue; }
+		if (slot < 0) { atomicOr(P.err, PL_ERR_FULL); continue; }
 )GG";
 	emit_flushes(s, G, "lvals[rr][q][2 * %d]");
 	s += "\t}\n";
@@ -1258,7 +1084,7 @@ static void emit_body_baked(std::string &s, const Gen &G)
 			nmiss++;
 	}
 	if (nmiss)
-		atomicOr(P.err, 2ull);
+		atomicOr(P.err, PL_ERR_BAKE_MISS);
 	if (tmask)
 		atomicOr(&btouch, tmask);
 	__syncthreads();
@@ -1266,9 +1092,9 @@ static void emit_body_baked(std::string &s, const Gen &G)
 	{
 		if (!((btouch >> q) & 1u))
 			continue;
-		int64_t slot = gg_slot(P, GC[q]);
+		int64_t slot = pl_slot(P, GC[q]);
 
-		if (slot < 0) { atomicOr(P.err, 1ull); continue; }
+		if (slot < 0) { atomicOr(P.err, PL_ERR_FULL); continue; }
 )GG";
 	emit_flushes(s, G, "lvals[rr * LPAD + (q * NA + %d) * LW]");
 	s += "\t}\n";

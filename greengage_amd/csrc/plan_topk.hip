@@ -43,8 +43,6 @@
 namespace gg
 {
 
-static constexpr unsigned long long PL_MSB = 0x8000000000000000ull;
-
 extern "C" int
 gg_engine_plan_topk_tile(void)
 {
@@ -103,7 +101,7 @@ pl_order_words(const PlanTopkDev &K, const PlanOrderEnt &E,
 	else
 	{
 		/* the MAX word is x ^ MSB, the MIN word its complement
-		 * (engine_internal.h PlanAggDev): x ^ MSB is the word wanted */
+		 * (plan_dev.h PlanAggDev): x ^ MSB is the word wanted */
 		unsigned long long e = row[1 + 2 * E.slot];
 
 		null = row[1 + 2 * E.cnt] == 0;

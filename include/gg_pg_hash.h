@@ -33,7 +33,18 @@
 #ifndef GG_PG_HASH_H
 #define GG_PG_HASH_H
 
+/* hipRTC (the generated plan programs carry this header's text) can include
+ * nothing; the fixed-width names are then typedef'd here */
+#ifdef __HIPCC_RTC__
+typedef long long int64_t;
+typedef unsigned long long uint64_t;
+typedef unsigned int uint32_t;
+typedef int int32_t;
+typedef unsigned char uint8_t;
+typedef signed char int8_t;
+#else
 #include <stdint.h>
+#endif
 
 #if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
 #define GG_HOSTDEV __host__ __device__ static inline

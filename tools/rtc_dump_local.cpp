@@ -46,6 +46,9 @@
  *   linner hashed LEFT join, and a dense INNER join chained through it
  *   ll     dense LEFT join, and a dense LEFT join chained through it
  *   lln    the same with the second join hashed on a nullable probe key
+ *   wh     Q1 shape with a dense INNER join and WHERE clauses: a scan clause
+ *          (disc in a range OR qty <= tax) and a post-join clause over a
+ *          nullable payload column; generic + baked fast tier
  *   all    every shape above, DUMPFILE used as a prefix: <prefix><shape>.cu
  * Exit status is non-zero when a variant fails to COMPILE (a module
  * load / function lookup failure without a GPU is not a failure). */
@@ -256,6 +259,7 @@ dump_shape(const char *shape, const char *file)
 	const long long *codes = nullptr;
 	int nbake = 0;
 	PlanDev D{};
+	PlanWhereDev W{};
 	std::shared_ptr<void> out;
 
 	setenv("GG_PLAN_RTC_DUMP", file, 1);
@@ -439,6 +443,34 @@ dump_shape(const char *shape, const char *file)
 		codes = gpcodes;
 		nbake = 3;
 	}
+	else if (!std::strcmp(shape, "wh"))
+	{
+		shape_q1(D, false);
+		join_dense(set_join(D, 0, GG_JOIN_INNER, 8));
+		W.atoms[0].col = dummy + DISC;
+		W.atoms[0].width = 8;
+		W.atoms[0].lo = 5;
+		W.atoms[0].hi = 8;
+		W.atoms[0].kind = GG_ATOM_RANGE;
+		W.atoms[1].col = dummy + QTY;
+		W.atoms[1].col2 = dummy + TAX;
+		W.atoms[1].width = W.atoms[1].width2 = 8;
+		W.atoms[1].kind = GG_ATOM_LE;
+		/* o_orderdate (int32) of the joined orders row, nullable */
+		W.atoms[2].col = dummy + 200;
+		W.atoms[2].nulls = (const uint8_t *) dummy + 208;
+		W.atoms[2].width = 4;
+		W.atoms[2].src = 1;
+		W.atoms[2].lo = 8035;
+		W.atoms[2].hi = 8401;
+		W.atoms[2].kind = GG_ATOM_NOT_RANGE;
+		W.natoms[0] = 2;
+		W.natoms[1] = 1;
+		W.nclauses = 2;
+		W.nscan = 1;
+		codes = q1codes;
+		nbake = 6;
+	}
 	else if (!std::strcmp(shape, "lrepl"))
 	{
 		setenv("GG_PLAN_LREPL", "32", 1);
@@ -454,7 +486,8 @@ dump_shape(const char *shape, const char *file)
 	}
 
 	bool gn0 = D.gnulls[0] != nullptr, gn1 = D.gnulls[1] != nullptr;
-	gg_status s1 = plan_rtc_compile(D, gn0, gn1, &out);
+	const PlanWhereDev *Wp = W.nclauses ? &W : nullptr;
+	gg_status s1 = plan_rtc_compile(D, gn0, gn1, &out, nullptr, 0, false, Wp);
 	bool ok = compiled(s1);
 
 	if (!ok)
@@ -463,7 +496,7 @@ dump_shape(const char *shape, const char *file)
 	if (nbake)
 	{
 		gg_status s2 = plan_rtc_compile(D, gn0, gn1, &out, codes,
-						nbake, !wide);
+						nbake, !wide, Wp);
 
 		if (!compiled(s2))
 		{
@@ -485,7 +518,7 @@ main(int argc, char **argv)
 	static const char *const all[] = {"q1", "q1w", "q6", "q1mm", "q1mmw",
 		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl", "q1f", "pvf",
 		"left", "lefth", "year", "yearl", "innh", "lsemi", "linner", "ll",
-		"lln"};
+		"lln", "wh"};
 	const char *file = argc > 1 ? argv[1] : "/tmp/rtc_dump.cu";
 	const char *shape = argc > 2 ? argv[2] : "q1";
 	bool ok = true;
