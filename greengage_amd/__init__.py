@@ -7,6 +7,7 @@ there is NO CPU fallback: on a machine with a GPU, a missing or
 unloadable engine library raises immediately.
 """
 from .engine import (  # noqa: F401
+    AGG_COUNT_DISTINCT,
     ATOM_EQ,
     ATOM_IS_NULL,
     ATOM_LE,

@@ -18,6 +18,8 @@
 #include "../../include/gg_result.h"
 #include "plan_dev.h"
 #include "plan_having.h"
+#include "plan_keys.h"
+#include "plan_distinct.h"
 #include "q1_pack.h"
 
 namespace gg
@@ -699,39 +701,7 @@ hipError_t launch_plan_compact(hipStream_t s,
 			       unsigned long long *out,
 			       unsigned long long *out_n, uint64_t cap);
 
-/* The group keys a code stands for (a NULL key is GG_PLAN_NULL_KEY).  ONE
- * definition for both sides: plan.cpp decodes every arena row with it, and
- * the device top-k (plan_topk.hip) decodes the order's key entries with it,
- * so the host comparator and the device sort keys cannot drift apart. */
-__host__ __device__ static inline void
-plan_keys_of(const PlanGroupPackDev &G, int ngroup, long long code,
-	     int64_t *k0, int64_t *k1)
-{
-	if (G.packed)
-	{
-		/* (e0 << shift) | e1; e = 0 is NULL, else the
-		 * value's offset from the column minimum, plus 1 */
-		uint64_t e0 = (uint64_t) code >> G.shift;
-		uint64_t e1 = (uint64_t) code & ((1ull << G.shift) - 1);
-
-		*k0 = e0 ? (int64_t) ((uint64_t) G.gmin[0] + e0 - 1)
-			: GG_PLAN_NULL_KEY;
-		*k1 = e1 ? (int64_t) ((uint64_t) G.gmin[1] + e1 - 1)
-			: GG_PLAN_NULL_KEY;
-	}
-	else if (ngroup == 2)
-	{
-		long long e0 = code / 512, e1 = code % 512;
-
-		*k0 = e0 == 256 ? GG_PLAN_NULL_KEY : e0;
-		*k1 = e1 == 256 ? GG_PLAN_NULL_KEY : e1;
-	}
-	else
-	{
-		*k0 = code;
-		*k1 = 0;
-	}
-}
+/* plan_keys_of, the group keys a code stands for, is plan_keys.h's */
 
 /* ---- device top-k over the compacted group rows (plan_topk.hip) ----
  * One resolved entry of gg_plan_desc.order[]: which words of a compacted
@@ -804,6 +774,18 @@ hipError_t launch_plan_having_gather(hipStream_t s,
 				     uint64_t ng, int rowsz,
 				     const uint32_t *idx, uint64_t ns,
 				     unsigned long long *out);
+
+/* ---- device regroup behind a COUNT(DISTINCT) plan (plan_distinct.hip;
+ * PlanRegroupDev and the fold's functions are plan_distinct.h's) ----
+ * Folds the ng_in compacted inner rows into the outer group table tkeys /
+ * tvals of nslots slots (a power of two; the caller resets it, and sizes it
+ * so that it cannot fill: PL_ERR_FULL in *err otherwise).
+ * launch_plan_compact over that table gives the outer rows. */
+hipError_t launch_plan_regroup(hipStream_t s, const PlanRegroupDev &G,
+			       const unsigned long long *rows, uint64_t ng_in,
+			       int rowsz, unsigned long long *tkeys,
+			       unsigned long long *tvals, uint64_t nslots,
+			       unsigned long long *err);
 
 /* plan.cpp */
 gg_status exec_plan(Pipeline *p, void *arena, size_t bytes,

@@ -90,6 +90,15 @@ struct PlanResolved
 	 * words; the device selection and the host filter both evaluate hv */
 	PlanHavingDev hv = {};
 	bool has_having = false;
+	/* COUNT(DISTINCT) (engine_abi.h gg_plan_aggkind): `dev` is then the
+	 * INNER plan, whose last group column is the distinct column, and
+	 * exec_plan regroups its groups by the descriptor's own group columns.
+	 * out_ngroup = the descriptor's ngroup, what everything behind the
+	 * regroup decodes keys by (dev.ngroup for every other plan); rg = the
+	 * fold's view of the inner rows, rg.dmask the distinct slots (0 = no
+	 * DISTINCT aggregate), rg.gp copied from dev.gp once that is resolved */
+	int out_ngroup = 0;
+	PlanRegroupDev rg = {};
 };
 
 static int coltype_width(gg_coltype t)
@@ -555,11 +564,6 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 		R->pred_bytes_per_row += col_bytes(c->dev, d->group_src[g],
 						   R->dev.gwidth[g]);
 	}
-	/* two char1 columns keep the e0 * 512 + e1 code; every other pair
-	 * is packed by the columns' ranges, resolved at the first execute */
-	R->dev.gp.packed = d->ngroup == 2 &&
-		!(R->dev.gwidth[0] == 1 && R->dev.gwidth[1] == 1);
-
 	/* aggregate filters: every one is validated and resolved, referenced
 	 * or not; only the referenced ones (fl.used, set below) are ever
 	 * evaluated or counted in pred_bytes_per_row */
@@ -584,6 +588,9 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 
 	int nacc = 0;
 	std::vector<int> helpers;	/* helper count slots so far */
+	/* the one column the DISTINCT aggregates count, and its source */
+	Table::Col *dcol = nullptr;
+	int dsrc = 0;
 
 	for (int a = 0; a < d->naggs; a++)
 	{
@@ -591,7 +598,7 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 		PlanAggDev T;
 
 		std::memset(&T, 0, sizeof(T));
-		if (A->kind < 0 || A->kind > GG_AGG_AVG)
+		if (A->kind < 0 || A->kind > GG_AGG_COUNT_DISTINCT)
 			return fail(GG_ENOTSUP, "plan: agg %d kind", a);
 		if (A->filter < 0 || A->filter > d->nfilters)
 			return fail(GG_EINVAL, "plan: agg %d names filter %d, "
@@ -601,6 +608,24 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 			return fail(GG_EINVAL, "plan: agg %d references filter "
 				    "%d, which has no predicates", a,
 				    A->filter - 1);
+		if (A->kind == GG_AGG_COUNT_DISTINCT)
+		{
+			if (A->nfactors != 1)
+				return fail(GG_ENOTSUP, "plan: agg %d: COUNT(DISTINCT) "
+					    "takes exactly one column, not %d factors "
+					    "(fall back to standard_ExecutorRun)", a,
+					    A->nfactors);
+			if (A->mod[0] != GG_FMOD_ID)
+				return fail(GG_ENOTSUP, "plan: agg %d: COUNT(DISTINCT) "
+					    "takes a plain column, not factor mod %d "
+					    "(fall back to standard_ExecutorRun)", a,
+					    A->mod[0]);
+			if (d->ngroup == 2)
+				return fail(GG_ENOTSUP, "plan: agg %d: COUNT(DISTINCT) "
+					    "with two group columns (the inner group "
+					    "code holds two fields; fall back to "
+					    "standard_ExecutorRun)", a);
+		}
 		if (A->kind == GG_AGG_COUNT_STAR)
 			T.nf = 0;
 		else if (A->nfactors < 1 || A->nfactors > 3 ||
@@ -630,6 +655,16 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 			T.mod[f] = A->mod[f];
 			R->pred_bytes_per_row += col_bytes(c->dev, A->src[f],
 							   T.width[f]);
+			if (A->kind == GG_AGG_COUNT_DISTINCT)
+			{
+				if (dcol && (dcol != c || dsrc != A->src[f]))
+					return fail(GG_ENOTSUP, "plan: agg %d: "
+						    "COUNT(DISTINCT) over more than one "
+						    "column in one plan (fall back to "
+						    "standard_ExecutorRun)", a);
+				dcol = c;
+				dsrc = A->src[f];
+			}
 		}
 
 		/* lower onto accumulator slots; helper slots re-read the
@@ -651,6 +686,14 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 
 		if (A->kind <= GG_AGG_SUM)
 			O.slot = push(A->kind);
+		else if (A->kind == GG_AGG_COUNT_DISTINCT)
+		{
+			/* COUNT(x) per (group key, x) pair, under the aggregate's
+			 * filter: non-zero iff the value counts */
+			O.slot = push(GG_AGG_COUNT_COL);
+			if (O.slot >= 0)
+				R->rg.dmask |= 1u << O.slot;
+		}
 		else
 		{
 			O.slot = push(A->kind == GG_AGG_MIN ? 3
@@ -676,7 +719,8 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 				helpers.push_back(O.cnt);
 			}
 		}
-		if (O.slot < 0 || (A->kind > GG_AGG_SUM && O.cnt < 0))
+		if (O.slot < 0 || (A->kind > GG_AGG_SUM &&
+				   A->kind != GG_AGG_COUNT_DISTINCT && O.cnt < 0))
 			return fail(GG_ENOTSUP,
 				    "plan: aggregates need more than %d "
 				    "accumulator slots (MIN/MAX/AVG take two)",
@@ -685,6 +729,28 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 		R->out_slots += A->kind == GG_AGG_AVG ? 2 : 1;
 	}
 	R->dev.naggs = nacc;
+	R->out_ngroup = d->ngroup;
+	if (dcol)
+	{
+		/* the inner plan: the distinct column, read once more as the
+		 * last group column */
+		const int g = R->dev.ngroup++;
+
+		R->dev.gcol[g] = dcol->dev;
+		R->dev.gnulls[g] = (const uint8_t *) dcol->nulls;
+		R->dev.gwidth[g] = coltype_width(dcol->type);
+		R->dev.pl.gsrc[g] = (int8_t) dsrc;
+		R->pred_bytes_per_row += col_bytes(dcol->dev, dsrc,
+						   R->dev.gwidth[g]);
+		R->rg.ngroup = R->dev.ngroup;
+		R->rg.naggs = nacc;
+		for (int a = 0; a < nacc; a++)
+			R->rg.kind[a] = (int8_t) R->dev.aggs[a].kind;
+	}
+	/* two char1 columns keep the e0 * 512 + e1 code; every other pair
+	 * is packed by the columns' ranges, resolved at the first execute */
+	R->dev.gp.packed = R->dev.ngroup == 2 &&
+		!(R->dev.gwidth[0] == 1 && R->dev.gwidth[1] == 1);
 	for (int a = 0; a < nacc; a++)
 		if (R->dev.fl.afilt[a])
 			R->dev.fl.used |= 1 << (R->dev.fl.afilt[a] - 1);
@@ -1417,12 +1483,23 @@ plan_combine_segments(Engine &e, Pipeline *p, const PlanResolved *R,
 	return GG_OK;
 }
 
-/* the group keys a code stands for (a NULL key is GG_PLAN_NULL_KEY) */
-static void
-plan_keys_of(const PlanDev &D, long long code, int64_t *k0, int64_t *k1)
+/* How the rows behind the regroup of a COUNT(DISTINCT) plan carry their
+ * keys, which is how every row of any other plan does: the outer view of the
+ * plan.  An outer code is the raw value of the one group column, or 0, under
+ * no pack; R->dev stays the inner plan, which the next execute scans. */
+static PlanGroupPackDev
+plan_out_pack(const PlanResolved *R)
 {
-	/* the decoder the device top-k shares (engine_internal.h) */
-	plan_keys_of(D.gp, D.ngroup, code, k0, k1);
+	return R->rg.dmask ? PlanGroupPackDev{} : R->dev.gp;
+}
+
+/* the group keys an emitted row's code stands for (a NULL key is
+ * GG_PLAN_NULL_KEY) */
+static void
+plan_keys_of(const PlanResolved *R, long long code, int64_t *k0, int64_t *k1)
+{
+	/* the decoder the device top-k shares (plan_keys.h) */
+	plan_keys_of(plan_out_pack(R), R->out_ngroup, code, k0, k1);
 }
 
 /* the value order entry E reads from a compacted row; false = SQL NULL.
@@ -1441,7 +1518,7 @@ plan_order_val(const PlanResolved *R, const PlanOrderEnt &E,
 	{
 		int64_t k[2];
 
-		plan_keys_of(R->dev, (long long) row[0], &k[0], &k[1]);
+		plan_keys_of(R, (long long) row[0], &k[0], &k[1]);
 		*v = k[E.slot];
 		return k[E.slot] != GG_PLAN_NULL_KEY;
 	}
@@ -1477,8 +1554,8 @@ plan_order_before(const PlanResolved *R, const unsigned long long *a,
 	}
 	int64_t a0, a1, b0, b1;
 
-	plan_keys_of(R->dev, (long long) a[0], &a0, &a1);
-	plan_keys_of(R->dev, (long long) b[0], &b0, &b1);
+	plan_keys_of(R, (long long) a[0], &a0, &a1);
+	plan_keys_of(R, (long long) b[0], &b0, &b1);
 	return a0 != b0 ? a0 < b0 : a1 < b1;
 }
 
@@ -1507,9 +1584,9 @@ plan_write_arena(const PlanResolved *R,
 		{
 			int64_t a0, a1, b0, b1;
 
-			plan_keys_of(R->dev, (long long) rows[a * rowsz], &a0,
+			plan_keys_of(R, (long long) rows[a * rowsz], &a0,
 				     &a1);
-			plan_keys_of(R->dev, (long long) rows[b * rowsz], &b0,
+			plan_keys_of(R, (long long) rows[b * rowsz], &b0,
 				     &b1);
 			return a0 != b0 ? a0 < b0 : a1 < b1;
 		});
@@ -1540,7 +1617,7 @@ plan_write_arena(const PlanResolved *R,
 	{
 		uint8_t *w = (uint8_t *) arena;
 		int64_t ng64 = (int64_t) ng;
-		int32_t na32 = R->out_slots, ngc32 = R->dev.ngroup;
+		int32_t na32 = R->out_slots, ngc32 = R->out_ngroup;
 
 		std::memcpy(w, &ng64, 8);
 		std::memcpy(w + 8, &na32, 4);
@@ -1551,7 +1628,7 @@ plan_write_arena(const PlanResolved *R,
 			size_t i = order[oi];
 			int64_t k0, k1;
 
-			plan_keys_of(R->dev, (long long) rows[i * rowsz], &k0,
+			plan_keys_of(R, (long long) rows[i * rowsz], &k0,
 				     &k1);
 			std::memcpy(w, &k0, 8);
 			std::memcpy(w + 8, &k1, 8);
@@ -1626,8 +1703,8 @@ plan_topk_device(Engine &e, Pipeline *p, const PlanResolved *R,
 	K.rowsz = rowsz;
 	K.norder = R->norder;
 	K.limit = (int) limit;
-	K.ngroup = R->dev.ngroup;
-	K.gp = R->dev.gp;
+	K.ngroup = R->out_ngroup;
+	K.gp = plan_out_pack(R);
 	for (int o = 0; o < R->norder; o++)
 		K.ord[o] = R->ord[o];
 
@@ -1775,6 +1852,74 @@ plan_having_fetch(Engine &e, Pipeline *p, const PlanResolved *R,
 	return GG_OK;
 }
 
+/* 3''. device regroup of a COUNT(DISTINCT) plan (plan_distinct.hip): folds
+ * the ng inner groups in dout, one per (group key, value) pair, into the
+ * plan's own groups; on return dout / ng are those, rows of the same size */
+static gg_status
+plan_regroup_device(Engine &e, Pipeline *p, const PlanResolved *R,
+		    unsigned long long *ctr, unsigned long long **dout_p,
+		    unsigned long long *ng_p)
+{
+	const unsigned long long ng_in = *ng_p;
+	const int naggs = R->dev.naggs, rowsz = plan_rowsz(R);
+	/* there are never more groups than pairs, so a table of 2 * pairs
+	 * slots cannot fill; without a group column there is one group */
+	const uint64_t nslots = R->out_ngroup == 0 ? 1
+		: next_pow2_pl(2 * (uint64_t) ng_in);
+	const char *nm[3] = {"plan.rg.tkeys", "plan.rg.tvals", "plan.rg.out"};
+	const size_t want[3] = {nslots * 8, nslots * (size_t) naggs * 16,
+				nslots * (size_t) rowsz * 8};
+	size_t fr = 0, tot = 0, held = 0, need = 0;
+	unsigned long long ng = 0, herr = 0;
+
+	/* the check a grown group table gets (plan_scan_groups) */
+	for (int i = 0; i < 3; i++)
+		if (p->ssize(nm[i]) < want[i])
+		{
+			held += p->ssize(nm[i]);
+			need += want[i];
+		}
+	GG_HIP(hipMemGetInfo(&fr, &tot));
+	if (need > fr + held)
+		return fail(GG_ENOTSUP,
+			    "plan: a regroup table of %llu slots needs %zu bytes "
+			    "with its output, %zu are free (fall back to "
+			    "standard_ExecutorRun)", (unsigned long long) nslots,
+			    need, fr + held);
+	unsigned long long *tkeys = (unsigned long long *)
+		p->sget(nm[0], want[0]);
+	unsigned long long *tvals = (unsigned long long *)
+		p->sget(nm[1], want[1]);
+	unsigned long long *out = (unsigned long long *)
+		p->sget(nm[2], want[2]);
+
+	if (!tkeys || !tvals || !out)
+		return fail(GG_ENOMEM, "plan regroup table");
+	{
+		Timed tm(e.stream);
+
+		GG_HIP(launch_fill_u64(e.stream, tkeys, nslots, PL_EMPTY));
+		GG_HIP(hipMemsetAsync(tvals, 0, want[1], e.stream));
+		GG_HIP(launch_plan_regroup(e.stream, R->rg, *dout_p, ng_in,
+					   rowsz, tkeys, tvals, nslots,
+					   R->dev.err));
+		GG_HIP(hipMemsetAsync(ctr, 0, 8, e.stream));
+		GG_HIP(launch_plan_compact(e.stream, tkeys, tvals, nslots, naggs,
+					   out, ctr, nslots));
+		double ms = tm.stop();
+
+		GG_HIP(hipStreamSynchronize(e.stream));
+		GG_HIP(hipMemcpy(&herr, R->dev.err, 8, hipMemcpyDeviceToHost));
+		GG_HIP(hipMemcpy(&ng, ctr, 8, hipMemcpyDeviceToHost));
+		p->stat("plan_regroup").add(ms, (int64_t) ng_in, (int64_t) ng);
+	}
+	if (herr || ng > nslots)
+		return fail(GG_ESTATE, "plan regroup table overflow");
+	*dout_p = out;
+	*ng_p = ng;
+	return GG_OK;
+}
+
 gg_status
 exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 {
@@ -1799,6 +1944,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
 	if (R->dev.gp.packed)
 		GG_TRY(plan_group_pack(e, p, R));
+	R->rg.gp = R->dev.gp;
 
 	unsigned long long *dout = nullptr, ng = 0;
 	std::vector<unsigned long long> rows;
@@ -1809,6 +1955,27 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		p->stat("path_plan_where").launches++;
 	GG_TRY(plan_build_joins(e, p, R, ctr));
 	GG_TRY(plan_scan_groups(e, p, R, ctr, &dout, &ng));
+	/* COUNT(DISTINCT): dout holds the inner plan's (group key, value)
+	 * pairs.  They are regrouped on the device with one segment (a pair
+	 * seen on two segments counts once, which only the combine by inner
+	 * code knows) and more than the handful of pairs the second-stage bake
+	 * wants whole on the host; else on the host, below, which then also
+	 * evaluates the HAVING and the order */
+	const bool distinct = R->rg.dmask != 0;
+	bool dhost = false;
+
+	if (distinct)
+	{
+		/* read once per execute, like GG_PLAN_TOPK */
+		const char *dv = getenv("GG_PLAN_DISTINCT");
+
+		dhost = !(e.cfg.n_segments == 1 && ng > 8 &&
+			  !(dv && !strcmp(dv, "host")));
+		p->stat(dhost ? "path_plan_distinct_host"
+			: "path_plan_distinct_device").launches++;
+		if (!dhost)
+			GG_TRY(plan_regroup_device(e, p, R, ctr, &dout, &ng));
+	}
 	/* HAVING on the device: one segment (a group's partial states prove
 	 * nothing ahead of the combine) and, as for the top-k, more than the
 	 * handful of groups the second-stage bake wants whole on the host */
@@ -1822,7 +1989,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		const char *hv = getenv("GG_PLAN_HAVING");
 
 		hvdev = e.cfg.n_segments == 1 && ng > 8 && ng < PL_TOPK_PAD &&
-			!(hv && !strcmp(hv, "host"));
+			!(hv && !strcmp(hv, "host")) && !dhost;
 		p->stat(hvdev ? "path_plan_having_device"
 			: "path_plan_having_host").launches++;
 		if (hvdev)
@@ -1841,7 +2008,8 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 			R->limit <= GG_PLAN_MAX_LIMIT &&
 			ns > (uint64_t) R->limit && ng > 8 &&
 			ng < PL_TOPK_PAD && !(tk && !strcmp(tk, "host")) &&
-			(hvdev || !R->has_having) && plan_topk_fits(e, R);
+			(hvdev || !R->has_having) && !dhost &&
+			plan_topk_fits(e, R);
 		p->stat(topk ? "path_plan_topk_device"
 			: "path_plan_topk_host").launches++;
 	}
@@ -1853,6 +2021,22 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		GG_TRY(plan_fetch_rows(R, dout, ng, rows));
 	if (e.cfg.n_segments > 1)
 		GG_TRY(plan_combine_segments(e, p, R, dout, rows));
+	if (dhost)
+	{
+		/* the host's regroup: the bake first, from the FULL set of
+		 * inner groups, then the fold the device runs.  A plan without
+		 * a group column yields its one row from no pairs at all */
+		std::vector<unsigned long long> outer;
+		const int rowsz = plan_rowsz(R);
+
+		plan_bake(e, p, R, rows);
+		plan_regroup_rows(R->rg, rows, &outer);
+		if (outer.empty() && R->out_ngroup == 0)
+			outer.assign(rowsz, 0);
+		p->stat("plan_regroup").add(0.0, (int64_t) (rows.size() / rowsz),
+					    (int64_t) (outer.size() / rowsz));
+		rows.swap(outer);
+	}
 	if (R->has_having && !hvdev)
 	{
 		/* the host's HAVING: the bake first, from the FULL group set
@@ -1861,7 +2045,8 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		const int rowsz = plan_rowsz(R);
 		size_t keep = 0;
 
-		plan_bake(e, p, R, rows);
+		if (!distinct)
+			plan_bake(e, p, R, rows);
 		for (size_t i = 0; i < rows.size() / rowsz; i++)
 			if (plan_having_row(R->hv, &rows[i * rowsz]))
 			{
@@ -1875,8 +2060,9 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 	}
 	GG_TRY(plan_write_arena(R, rows, arena, bytes, written));
 	/* the bake wants the whole group set: a top-k left only its head, a
-	 * device HAVING only its survivors, and the host's HAVING baked above */
-	if (!topk && !R->has_having)
+	 * device HAVING only its survivors, and the host's HAVING baked above;
+	 * behind a regroup the rows are not the scan's groups at all */
+	if (!topk && !R->has_having && !distinct)
 		plan_bake(e, p, R, rows);
 	return GG_OK;
 }

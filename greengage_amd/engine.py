@@ -152,6 +152,7 @@ PLAN_NULL_KEY = -(1 << 63) + 1
 # gg_plan_aggkind (engine_abi.h)
 AGG_COUNT_STAR, AGG_COUNT_COL, AGG_SUM = 0, 1, 2
 AGG_MIN, AGG_MAX, AGG_AVG = 3, 4, 5
+AGG_COUNT_DISTINCT = 6
 # gg_plan_joinkind (engine_abi.h)
 JOIN_SEMI, JOIN_INNER = 0, 1
 JOIN_LEFT, JOIN_ANTI = 2, 3
@@ -185,7 +186,7 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
            (plan_group_bits).  The ranges are resolved at the first
            execute_plan, which raises EngineError status 5 for a
            pair that does not fit.
-    aggs: ["count"] | ("count", col) |
+    aggs: ["count"] | ("count", col) | ("count_distinct", col) |
           ("sum", [(col, "id"|"sub100"|"add100"), ...]) |
           ("min", (col, mod)) | ("max", (col, mod)) |
           ("avg", [(col, mod), ...]) |
@@ -194,7 +195,13 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
           sees only the surviving rows on which every half-open range
           holds (a NULL value fails it).  Groups are unaffected; a group
           with no passing row reports COUNT 0, SUM 0, MIN/MAX None,
-          AVG (0, 0).  Equal predicate lists share one entry of the
+          AVG (0, 0), COUNT(DISTINCT) 0.  ("count_distinct", col) counts
+          the distinct non-NULL values of one column per group; with a
+          filter, a value counts if some row carrying it passes.  It goes
+          with at most one group column, and every count_distinct of a
+          plan names the same column (the engine refuses the rest with
+          status 5); est_groups then estimates the distinct (group key,
+          value) pairs.  Equal predicate lists share one entry of the
           descriptor's filters[]; more than PLAN_MAX_FILTERS distinct
           lists, or more than PLAN_MAX_FILTER_PREDS ranges in one, raise
           ValueError.
@@ -270,6 +277,16 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
         if spec == "count" or spec == ("count",):
             d.aggs[a].kind = AGG_COUNT_STAR
             d.aggs[a].nfactors = 0
+        elif spec[0] == "count_distinct":
+            # one plain column; a factor LIST [(col, mod), ...] is passed
+            # through so the engine's rejections are reachable
+            fs = (list(spec[1]) if isinstance(spec[1], list)
+                  else [(spec[1], "id")])
+            d.aggs[a].kind = AGG_COUNT_DISTINCT
+            d.aggs[a].nfactors = len(fs)
+            for f, (c, m) in enumerate(fs):
+                d.aggs[a].col[f], d.aggs[a].src[f] = colref(c)
+                d.aggs[a].mod[f] = mods[m]
         elif spec[0] == "count":
             d.aggs[a].kind = AGG_COUNT_COL
             d.aggs[a].nfactors = 1
@@ -903,8 +920,9 @@ class Engine:
     def execute_plan(self, p, max_groups=1 << 16):
         """One (key0, key1, vals) per group, in arena order: by (key0,
         key1), or as the plan's order_by / limit say.  vals holds one entry
-        per descriptor aggregate: COUNT/SUM -> int, MIN/MAX -> int or None
-        (SQL NULL), AVG -> (sum, count) for avg_str."""
+        per descriptor aggregate: COUNT, COUNT(DISTINCT), SUM -> int,
+        MIN/MAX -> int or None (SQL NULL), AVG -> (sum, count) for
+        avg_str."""
         kinds = self._plan_kinds.get(p)
         nslots_guess = 8 if kinds is None else max(
             8, sum(2 if k == AGG_AVG else 1 for k in kinds))

@@ -584,7 +584,39 @@ typedef struct gg_plan_join
  *
  * AVG(f0*f1*f2): 1..3 factors like SUM.  The transition state is the
  * exact 128-bit sum plus the count of rows whose factors are all
- * non-NULL (numeric_avg's state); finalise with gg_engine_avg_str. */
+ * non-NULL (numeric_avg's state); finalise with gg_engine_avg_str.
+ *
+ * COUNT(DISTINCT f0): the number of distinct non-NULL values of one column
+ * among the group's rows.  nfactors == 1 and mod[0] == GG_FMOD_ID, anything
+ * else is GG_ENOTSUP; the column is char1, int32 or int64 from any valid
+ * source, under the source rules and GG_EINVAL cases of any factor.  NULL
+ * inputs are not counted, the NULL-extended payload of a partnerless LEFT
+ * row included, and a group with no non-NULL input reports 0, never NULL.
+ * With a filter, a value counts iff at least one row of the group carrying
+ * it passes the filter and has it non-NULL (as for COUNT).  The result is
+ * one arena slot, a signed 128-bit count laid out like COUNT; HAVING atoms
+ * and order entries treat it exactly as a COUNT.  Any other aggregate kind
+ * may stand beside it.
+ *
+ * The plan is the reference's two-stage one (cdbgroup.c): an inner
+ * aggregation by (group key, value), which is an ordinary plan whose last
+ * group column is the distinct column, then a regroup by the group key
+ * alone, on the device ahead of HAVING and the order (one segment, more than
+ * 8 pairs) or on the host (GG_PLAN_DISTINCT=host in the environment forces
+ * the host).  So the value restrictions on the distinct column are those of
+ * a group column:
+ *   ngroup == 1  the pair (g, x) travels as the two-column code of
+ *                gg_plan_desc.group_cols, packed under the 62-bit budget; an
+ *                over-budget pair makes the first gg_engine_execute return
+ *                GG_ENOTSUP, every segment alike.  Two char1 columns keep
+ *                e0 * 512 + e1
+ *   ngroup == 0  the inner plan groups by x alone: values of INT64_MIN or
+ *                GG_PLAN_NULL_KEY are not supported
+ * Limits, each GG_ENOTSUP at compile: ngroup == 2 together with a DISTINCT
+ * aggregate (the inner code would need three fields), and DISTINCT
+ * aggregates over more than one (column, source) in one plan; several over
+ * the same column with different filters are accepted.  Each DISTINCT
+ * aggregate takes one accumulator slot of GG_PLAN_MAX_AGGS. */
 typedef enum gg_plan_aggkind
 {
 	GG_AGG_COUNT_STAR = 0,
@@ -592,8 +624,16 @@ typedef enum gg_plan_aggkind
 	GG_AGG_SUM = 2,
 	GG_AGG_MIN = 3,
 	GG_AGG_MAX = 4,
-	GG_AGG_AVG = 5
+	GG_AGG_AVG = 5,
+	/* the next value; pinned below, since it is ABI */
+	GG_AGG_COUNT_DISTINCT
 } gg_plan_aggkind;
+
+#ifdef __cplusplus
+static_assert(GG_AGG_COUNT_DISTINCT == 6, "gg_plan_aggkind values are ABI");
+#else
+_Static_assert(GG_AGG_COUNT_DISTINCT == 6, "gg_plan_aggkind values are ABI");
+#endif
 
 typedef enum gg_plan_fmod
 {
@@ -781,7 +821,11 @@ typedef struct gg_plan_desc
 	 * full, every further row of a new group probes ALL of it before
 	 * giving up, and the whole scan is then repeated.  That is what an
 	 * over-cap plan has always cost before failing; a good est_groups is
-	 * what avoids it. */
+	 * what avoids it.
+	 *
+	 * For a plan with a COUNT(DISTINCT) aggregate the group table holds
+	 * one entry per distinct (group key, value) pair, so the estimate is
+	 * of that count: Agg.numGroups of the inner Agg. */
 	int64_t est_groups;
 } gg_plan_desc;
 
