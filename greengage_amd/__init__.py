@@ -33,6 +33,7 @@ from .engine import (  # noqa: F401
     PLAN_MAX_CLAUSES,
     PLAN_MAX_FILTERS,
     PLAN_MAX_FILTER_PREDS,
+    PLAN_MAX_GROUP_COLS,
     PLAN_MAX_HAVING_ATOMS,
     PLAN_MAX_HAVING_CLAUSES,
     PLAN_MAX_HAVING_TOTAL,
@@ -40,10 +41,12 @@ from .engine import (  # noqa: F401
     PLAN_MAX_ORDER,
     PLAN_MAX_WHERE_ATOMS,
     build_plan_desc,
+    build_plan_groups,
     build_plan_having,
     build_plan_where,
     pgdate,
     plan_group_bits,
+    plan_group_bits_n,
     plan_topk_tile,
 )
 

@@ -668,6 +668,9 @@ static_assert(offsetof(PlanDev, fl) ==
 	      "PlanFilterDev follows PlanGroupPackDev without padding");
 static_assert(sizeof(PlanWhereDev) % 8 == 0 && alignof(PlanWhereDev) == 8,
 	      "PlanWhereDev follows PlanDev's bytes without padding");
+static_assert(PL_MAX_GCOLS == GG_PLAN_MAX_GROUP_COLS &&
+	      sizeof(PlanGroupNDev) % 8 == 0 && alignof(PlanGroupNDev) == 8,
+	      "PlanGroupNDev follows PlanWhereDev's bytes without padding");
 
 struct PlanBuildDev
 {
@@ -691,9 +694,11 @@ struct PlanBuildDev
  * every plan kernel, interpreted or generated */
 int pl_grid(int64_t n);
 hipError_t launch_plan_build(hipStream_t s, const PlanBuildDev &b);
-/* w = the plan's scope-0 WHERE clauses, nullptr for a plan without any */
+/* w = the plan's scope-0 WHERE clauses, nullptr for a plan without any;
+ * gn = the block of a plan with three or four group columns, else nullptr */
 hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p,
-				const PlanWhereDev *w = nullptr);
+				const PlanWhereDev *w = nullptr,
+				const PlanGroupNDev *gn = nullptr);
 hipError_t launch_plan_compact(hipStream_t s,
 			       const unsigned long long *tkeys,
 			       const unsigned long long *tvals,
@@ -708,7 +713,7 @@ hipError_t launch_plan_compact(hipStream_t s,
  * row (code, naggs x (lo, hi)) it reads and how they compare. */
 enum PlanOrderKind
 {
-	PL_ORD_KEY = 0,		/* decoded group key `slot` (0 or 1) */
+	PL_ORD_KEY = 0,		/* decoded group key `slot` (0 .. 3) */
 	PL_ORD_I128 = 1,	/* COUNT / SUM: accumulator `slot`, signed
 				 * 128-bit, never NULL */
 	PL_ORD_MIN = 2,		/* MIN / MAX: order-encoded word in `slot`, */
@@ -734,6 +739,7 @@ struct PlanTopkDev
 	int ngroup;
 	PlanGroupPackDev gp;
 	PlanOrderEnt ord[GG_PLAN_MAX_ORDER];
+	PlanKeysN kn;		/* n >= 3: the code holds n packed fields */
 };
 
 /* rows per tournament tile, threads per tile, "no row" */
@@ -800,11 +806,14 @@ gg_status exec_plan(Pipeline *p, void *arena, size_t bytes,
 gg_status plan_rtc_compile(const PlanDev &D, bool has_gnull0,
 			   bool has_gnull1, std::shared_ptr<void> *out,
 			   const long long *bake = nullptr, int nbake = 0,
-			   bool fast = false, const PlanWhereDev *W = nullptr);
-/* W must be what the kernel was compiled with (nullptr = no clauses) */
+			   bool fast = false, const PlanWhereDev *W = nullptr,
+			   const PlanGroupNDev *N = nullptr);
+/* W and N must be what the kernel was compiled with (nullptr = no clauses,
+ * at most two group columns) */
 gg_status plan_rtc_launch(hipStream_t s, const std::shared_ptr<void> &h,
 			  const PlanDev &P, int grid, int block,
-			  const PlanWhereDev *W = nullptr);
+			  const PlanWhereDev *W = nullptr,
+			  const PlanGroupNDev *N = nullptr);
 
 /* comm.cpp */
 gg_status comm_make_id(void *out_id128);

@@ -68,7 +68,13 @@ struct PlanResolved
 	 * resolved, 1 = resolved and within budget, 2 = over budget; the
 	 * widths are kept for the refusal's message */
 	int gp_state = 0;
-	int gp_bits[2] = {0, 0};
+	int gp_bits[GG_PLAN_MAX_GROUP_COLS] = {0, 0, 0, 0};
+	/* three or four group columns (gg_plan_groups): columns 2 and 3 and the
+	 * N-field code's parameters, which gp_state covers as it does the
+	 * pair's; has_gn = gn.k.n >= 3.  dev.ngroup stays 2 (the columns held by
+	 * dev itself) and dev.gp.packed 0; out_ngroup is G */
+	PlanGroupNDev gn = {};
+	bool has_gn = false;
 	/* ORDER BY / LIMIT (gg_plan_desc.order / limit), the order's entries
 	 * resolved onto compacted-row words; the device top-k reads the same
 	 * entries (engine_internal.h PlanOrderEnt) */
@@ -141,22 +147,40 @@ gg_engine_plan_desc_size(void)
  * it cannot overflow; span + 1 values plus the NULL code need
  * bit_length(span + 1) bits, 65 where span + 1 is 2^64 itself. */
 extern "C" gg_status
+gg_engine_plan_group_bits_n(int n, const int64_t *mn, const int64_t *mx,
+			    int *bits)
+{
+	int total = 0;
+
+	if (n < 1 || n > GG_PLAN_MAX_GROUP_COLS || !mn || !mx || !bits)
+		return fail(GG_EINVAL, "plan group bits: %d columns", n);
+	for (int g = 0; g < n; g++)
+	{
+		if (mn[g] > mx[g])	/* no rows */
+			bits[g] = 1;
+		else
+		{
+			uint64_t span = (uint64_t) mx[g] - (uint64_t) mn[g];
+
+			bits[g] = span == UINT64_MAX ? 65
+				: 64 - __builtin_clzll(span + 1);
+		}
+		total += bits[g];	/* at most 4 x 65 */
+	}
+	return total <= 62 ? GG_OK : GG_ENOTSUP;
+}
+
+extern "C" gg_status
 gg_engine_plan_group_bits(const int64_t mn[2], const int64_t mx[2],
 			  int bits[2])
 {
-	for (int g = 0; g < 2; g++)
-	{
-		if (mn[g] > mx[g])	/* no rows */
-		{
-			bits[g] = 1;
-			continue;
-		}
-		uint64_t span = (uint64_t) mx[g] - (uint64_t) mn[g];
+	return gg_engine_plan_group_bits_n(2, mn, mx, bits);
+}
 
-		bits[g] = span == UINT64_MAX ? 65
-			: 64 - __builtin_clzll(span + 1);
-	}
-	return bits[0] + bits[1] <= 62 ? GG_OK : GG_ENOTSUP;
+extern "C" size_t
+gg_engine_plan_groups_size(void)
+{
+	return sizeof(gg_plan_groups);
 }
 
 /* the table a column source names (engine_abi.h "column sources"):
@@ -421,7 +445,8 @@ check_having(const gg_plan_desc *d, const gg_plan_having *h)
 
 static gg_status
 plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
-	     const gg_plan_having *h, gg_pipeline *out)
+	     const gg_plan_having *h, const gg_plan_groups *gs,
+	     gg_pipeline *out)
 {
 	Engine &e = engine();
 
@@ -440,6 +465,15 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 	    d->nfilters < 0 || d->nfilters > GG_PLAN_MAX_FILTERS)
 		return fail(GG_ENOTSUP, "plan: shape out of v1 bounds "
 			    "(fall back to standard_ExecutorRun)");
+
+	/* group columns 2 and 3 (gg_plan_groups) go with a full descriptor */
+	if (gs && (gs->ncols < 0 || gs->ncols > GG_PLAN_MAX_GROUP_COLS - 2))
+		return fail(GG_ENOTSUP, "plan: %d further group columns (fall "
+			    "back to standard_ExecutorRun)", gs->ncols);
+	if (gs && d->ngroup != 2)
+		return fail(GG_EINVAL, "plan: further group columns need "
+			    "ngroup == 2, not %d", d->ngroup);
+	const int ngtotal = d->ngroup + (gs ? gs->ncols : 0);
 
 	if (d->limit < 0 || d->norder < 0 || d->norder > GG_PLAN_MAX_ORDER ||
 	    d->est_groups < 0)
@@ -564,6 +598,28 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 		R->pred_bytes_per_row += col_bytes(c->dev, d->group_src[g],
 						   R->dev.gwidth[g]);
 	}
+	for (int g = 0; gs && g < gs->ncols; g++)
+	{
+		Table *gt = nullptr;
+
+		GG_TRY(resolve_src(d, scan, gs->src[g], d->njoins,
+				   "group_src", 2 + g, &gt));
+		Table::Col *c = gt->find(gs->cols[g] ? gs->cols[g] : "");
+
+		if (!c)
+			return fail(GG_EINVAL, "plan: group column missing");
+		R->gn.gcol[g] = c->dev;
+		R->gn.gnulls[g] = (const uint8_t *) c->nulls;
+		R->gn.gwidth[g] = coltype_width(c->type);
+		R->gn.gsrc[g] = gs->src[g];
+		R->pred_bytes_per_row += col_bytes(c->dev, gs->src[g],
+						   R->gn.gwidth[g]);
+	}
+	if (gs)
+	{
+		R->gn.k.n = ngtotal;
+		R->has_gn = true;
+	}
 	/* aggregate filters: every one is validated and resolved, referenced
 	 * or not; only the referenced ones (fl.used, set below) are ever
 	 * evaluated or counted in pred_bytes_per_row */
@@ -620,6 +676,11 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 					    "takes a plain column, not factor mod %d "
 					    "(fall back to standard_ExecutorRun)", a,
 					    A->mod[0]);
+			if (gs)
+				return fail(GG_ENOTSUP, "plan: agg %d: COUNT(DISTINCT) "
+					    "with %d group columns (the inner group "
+					    "code would hold a fifth field; fall back "
+					    "to standard_ExecutorRun)", a, ngtotal);
 			if (d->ngroup == 2)
 				return fail(GG_ENOTSUP, "plan: agg %d: COUNT(DISTINCT) "
 					    "with two group columns (the inner group "
@@ -729,7 +790,7 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 		R->out_slots += A->kind == GG_AGG_AVG ? 2 : 1;
 	}
 	R->dev.naggs = nacc;
-	R->out_ngroup = d->ngroup;
+	R->out_ngroup = ngtotal;
 	if (dcol)
 	{
 		/* the inner plan: the distinct column, read once more as the
@@ -749,7 +810,7 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 	}
 	/* two char1 columns keep the e0 * 512 + e1 code; every other pair
 	 * is packed by the columns' ranges, resolved at the first execute */
-	R->dev.gp.packed = R->dev.ngroup == 2 &&
+	R->dev.gp.packed = R->dev.ngroup == 2 && !R->has_gn &&
 		!(R->dev.gwidth[0] == 1 && R->dev.gwidth[1] == 1);
 	for (int a = 0; a < nacc; a++)
 		if (R->dev.fl.afilt[a])
@@ -772,10 +833,10 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 		E.nulls_first = O->nulls_first != 0;
 		if (O->what == 0)
 		{
-			if (O->index < 0 || O->index >= d->ngroup)
+			if (O->index < 0 || O->index >= ngtotal)
 				return fail(GG_EINVAL, "plan: order entry %d names "
 					    "group key %d, the plan has %d", o,
-					    O->index, d->ngroup);
+					    O->index, ngtotal);
 			E.kind = PL_ORD_KEY;
 			E.slot = O->index;
 		}
@@ -870,7 +931,7 @@ plan_compile(const gg_plan_desc *d, const gg_plan_where *w,
 extern "C" gg_status
 gg_engine_compile_plan(const gg_plan_desc *d, gg_pipeline *out)
 {
-	return plan_compile(d, nullptr, nullptr, out);
+	return plan_compile(d, nullptr, nullptr, nullptr, out);
 }
 
 extern "C" gg_status
@@ -880,7 +941,7 @@ gg_engine_compile_plan_where(const gg_plan_desc *d, const gg_plan_where *w,
 	/* no clauses: gg_engine_compile_plan exactly.  A count outside its
 	 * bounds is refused once the descriptor itself has been checked */
 	return plan_compile(d, w && w->nclauses != 0 ? w : nullptr, nullptr,
-			    out);
+			    nullptr, out);
 }
 
 extern "C" gg_status
@@ -889,7 +950,18 @@ gg_engine_compile_plan_having(const gg_plan_desc *d, const gg_plan_where *w,
 {
 	/* no clauses: gg_engine_compile_plan_where exactly */
 	return plan_compile(d, w && w->nclauses != 0 ? w : nullptr,
-			    h && h->nclauses != 0 ? h : nullptr, out);
+			    h && h->nclauses != 0 ? h : nullptr, nullptr, out);
+}
+
+extern "C" gg_status
+gg_engine_compile_plan_groups(const gg_plan_desc *d, const gg_plan_where *w,
+			      const gg_plan_having *h, const gg_plan_groups *g,
+			      gg_pipeline *out)
+{
+	/* no further columns: gg_engine_compile_plan_having exactly */
+	return plan_compile(d, w && w->nclauses != 0 ? w : nullptr,
+			    h && h->nclauses != 0 ? h : nullptr,
+			    g && g->ncols != 0 ? g : nullptr, out);
 }
 
 static uint64_t next_pow2_pl(uint64_t v)
@@ -928,11 +1000,12 @@ plan_scan_compact(Engine &e, Pipeline *p, const PlanResolved *R,
 	const PlanDev &D = R->dev;
 
 	const PlanWhereDev *W = R->where0 ? &R->wh : nullptr;
+	const PlanGroupNDev *N = R->has_gn ? &R->gn : nullptr;
 
 	if (k)
-		GG_TRY(plan_rtc_launch(e.stream, k, D, pl_grid(D.n), 256, W));
+		GG_TRY(plan_rtc_launch(e.stream, k, D, pl_grid(D.n), 256, W, N));
 	else
-		GG_HIP(launch_plan_scan_agg(e.stream, D, W));
+		GG_HIP(launch_plan_scan_agg(e.stream, D, W, N));
 	if (tm)
 		p->stat("plan_scan_agg").add(tm->stop(), R->scan_rows, 0,
 					     R->scan_rows *
@@ -1045,22 +1118,27 @@ plan_fast_tier_provable(Engine &e, const PlanResolved *R)
 static gg_status
 plan_group_pack(Engine &e, Pipeline *p, PlanResolved *R)
 {
+	/* the pair, or the G = 3 or 4 columns of a gg_plan_groups plan, whose
+	 * columns 2 and 3 live in R->gn */
+	const int G = R->has_gn ? R->gn.k.n : 2;
+
 	if (R->gp_state == 0)
 	{
 		int nseg = e.cfg.n_segments;
 		/* an empty column is the identity of the fold below */
-		int64_t mn[2] = {INT64_MAX, INT64_MAX};
-		int64_t mx[2] = {INT64_MIN, INT64_MIN};
+		int64_t mn[GG_PLAN_MAX_GROUP_COLS], mx[GG_PLAN_MAX_GROUP_COLS];
 
-		for (int g = 0; g < 2; g++)
+		for (int g = 0; g < G; g++)
 		{
-			int64_t rows = R->src_rows[R->dev.pl.gsrc[g]];
+			const PlanGroupCol C = plan_group_col(R->dev, R->gn, g);
+			int64_t rows = R->src_rows[C.src];
 			long long a, b;
 
+			mn[g] = INT64_MAX;
+			mx[g] = INT64_MIN;
 			if (rows <= 0)
 				continue;
-			GG_TRY(engine_col_minmax(e, R->dev.gcol[g],
-						 R->dev.gwidth[g], rows, &a, &b));
+			GG_TRY(engine_col_minmax(e, C.col, C.width, rows, &a, &b));
 			mn[g] = a;
 			mx[g] = b;
 		}
@@ -1069,30 +1147,58 @@ plan_group_pack(Engine &e, Pipeline *p, PlanResolved *R)
 			if (!comm_ready())
 				return fail(GG_ESTATE,
 					    "multi-segment plan without comm");
-			/* the ranges travel as their two's-complement words */
-			unsigned long long mine[4] = {
-				(unsigned long long) mn[0],
-				(unsigned long long) mx[0],
-				(unsigned long long) mn[1],
-				(unsigned long long) mx[1]};
+			/* the ranges travel as their two's-complement words, 2 * G
+			 * of them in one allgather */
+			unsigned long long mine[2 * GG_PLAN_MAX_GROUP_COLS];
 			std::vector<unsigned long long> all;
 
-			GG_TRY(allgather_host_u64(p, "plan.gprange", mine, 4,
+			for (int g = 0; g < G; g++)
+			{
+				mine[2 * g] = (unsigned long long) mn[g];
+				mine[2 * g + 1] = (unsigned long long) mx[g];
+			}
+			GG_TRY(allgather_host_u64(p, "plan.gprange", mine, 2 * G,
 						  all));
 			for (int r = 0; r < nseg; r++)
-				for (int g = 0; g < 2; g++)
+				for (int g = 0; g < G; g++)
 				{
 					mn[g] = std::min(mn[g], (int64_t)
-							 all[4 * r + 2 * g]);
+							 all[2 * G * r + 2 * g]);
 					mx[g] = std::max(mx[g], (int64_t)
-							 all[4 * r + 2 * g + 1]);
+							 all[2 * G * r + 2 * g + 1]);
 				}
 		}
-		R->gp_state = gg_engine_plan_group_bits(mn, mx, R->gp_bits)
+		R->gp_state = gg_engine_plan_group_bits_n(G, mn, mx, R->gp_bits)
 			== GG_OK ? 1 : 2;
-		for (int g = 0; g < 2; g++)
-			R->dev.gp.gmin[g] = mn[g] > mx[g] ? 0 : mn[g];
-		R->dev.gp.shift = R->gp_bits[1];
+		if (R->has_gn)
+		{
+			int below = 0;
+
+			/* field G-1 is the least significant */
+			for (int g = G - 1; g >= 0; g--)
+			{
+				R->gn.k.gmin[g] = mn[g] > mx[g] ? 0 : mn[g];
+				R->gn.k.shift[g] = R->gp_state == 1 ? below : 0;
+				below += R->gp_bits[g];
+			}
+		}
+		else
+		{
+			for (int g = 0; g < 2; g++)
+				R->dev.gp.gmin[g] = mn[g] > mx[g] ? 0 : mn[g];
+			R->dev.gp.shift = R->gp_bits[1];
+		}
+	}
+	if (R->gp_state == 2 && R->has_gn)
+	{
+		std::string w = std::to_string(R->gp_bits[0]);
+
+		for (int g = 1; g < G; g++)
+			w += " + " + std::to_string(R->gp_bits[g]);
+		return fail(GG_ENOTSUP,
+			    "plan: %d-column group key needs %s bits, the packed "
+			    "code holds 62 (fall back to standard_ExecutorRun)", G,
+			    w.c_str());
 	}
 	if (R->gp_state == 2)
 		return fail(GG_ENOTSUP,
@@ -1101,6 +1207,8 @@ plan_group_pack(Engine &e, Pipeline *p, PlanResolved *R)
 			    "standard_ExecutorRun)", R->gp_bits[0],
 			    R->gp_bits[1]);
 	p->stat("path_plan_group_packed").launches++;
+	if (R->has_gn)
+		p->stat("path_plan_group_packed_n").launches++;
 	return GG_OK;
 }
 
@@ -1314,7 +1422,8 @@ plan_scan_groups(Engine &e, Pipeline *p, PlanResolved *R,
 			gg_status rs = plan_rtc_compile(
 				R->dev, R->dev.gnulls[0] != nullptr,
 				R->dev.gnulls[1] != nullptr, &R->rtc, nullptr, 0,
-				false, R->where0 ? &R->wh : nullptr);
+				false, R->where0 ? &R->wh : nullptr,
+				R->has_gn ? &R->gn : nullptr);
 
 			R->rtc_tried = true;
 			p->stat(rs == GG_OK ? "path_plan_rtc"
@@ -1496,10 +1605,27 @@ plan_out_pack(const PlanResolved *R)
 /* the group keys an emitted row's code stands for (a NULL key is
  * GG_PLAN_NULL_KEY) */
 static void
-plan_keys_of(const PlanResolved *R, long long code, int64_t *k0, int64_t *k1)
+plan_keys_of(const PlanResolved *R, long long code,
+	     int64_t k[GG_PLAN_MAX_GROUP_COLS])
 {
 	/* the decoder the device top-k shares (plan_keys.h) */
-	plan_keys_of(plan_out_pack(R), R->out_ngroup, code, k0, k1);
+	plan_keys_of(plan_out_pack(R), R->gn.k, R->out_ngroup, code, k);
+}
+
+/* (key0 .. key3) ascending as raw int64: the order of an unordered plan's
+ * rows and every order's tie-break.  Keys past the plan's columns are 0 on
+ * both sides */
+static bool
+plan_keys_before(const PlanResolved *R, long long ca, long long cb)
+{
+	int64_t a[GG_PLAN_MAX_GROUP_COLS], b[GG_PLAN_MAX_GROUP_COLS];
+
+	plan_keys_of(R, ca, a);
+	plan_keys_of(R, cb, b);
+	for (int g = 0; g < GG_PLAN_MAX_GROUP_COLS - 1; g++)
+		if (a[g] != b[g])
+			return a[g] < b[g];
+	return a[GG_PLAN_MAX_GROUP_COLS - 1] < b[GG_PLAN_MAX_GROUP_COLS - 1];
 }
 
 /* the value order entry E reads from a compacted row; false = SQL NULL.
@@ -1516,9 +1642,9 @@ plan_order_val(const PlanResolved *R, const PlanOrderEnt &E,
 	}
 	if (E.kind == PL_ORD_KEY)
 	{
-		int64_t k[2];
+		int64_t k[GG_PLAN_MAX_GROUP_COLS];
 
-		plan_keys_of(R, (long long) row[0], &k[0], &k[1]);
+		plan_keys_of(R, (long long) row[0], k);
 		*v = k[E.slot];
 		return k[E.slot] != GG_PLAN_NULL_KEY;
 	}
@@ -1552,11 +1678,7 @@ plan_order_before(const PlanResolved *R, const unsigned long long *a,
 		if (ha && va != vb)
 			return (va < vb) != (E.desc != 0);
 	}
-	int64_t a0, a1, b0, b1;
-
-	plan_keys_of(R, (long long) a[0], &a0, &a1);
-	plan_keys_of(R, (long long) b[0], &b0, &b1);
-	return a0 != b0 ? a0 < b0 : a1 < b1;
+	return plan_keys_before(R, (long long) a[0], (long long) b[0]);
 }
 
 /* 5. order the groups and materialize the arena: by decoded keys, or by
@@ -1582,13 +1704,8 @@ plan_write_arena(const PlanResolved *R,
 		std::sort(order.begin(), order.end(),
 			  [&](size_t a, size_t b)
 		{
-			int64_t a0, a1, b0, b1;
-
-			plan_keys_of(R, (long long) rows[a * rowsz], &a0,
-				     &a1);
-			plan_keys_of(R, (long long) rows[b * rowsz], &b0,
-				     &b1);
-			return a0 != b0 ? a0 < b0 : a1 < b1;
+			return plan_keys_before(R, (long long) rows[a * rowsz],
+						(long long) rows[b * rowsz]);
 		});
 	else
 	{
@@ -1609,7 +1726,9 @@ plan_write_arena(const PlanResolved *R,
 			std::sort(order.begin(), order.end(), before);
 	}
 
-	size_t need = 16 + (size_t) ng * (16 + 16 * (size_t) R->out_slots);
+	/* a row carries two keys, or all G of a plan with more */
+	const size_t keyb = 8 * (size_t) std::max(2, R->out_ngroup);
+	size_t need = 16 + (size_t) ng * (keyb + 16 * (size_t) R->out_slots);
 
 	if (bytes < need)
 		return fail(GG_EINVAL, "plan arena too small (%zu < %zu)",
@@ -1626,13 +1745,11 @@ plan_write_arena(const PlanResolved *R,
 		for (size_t oi = 0; oi < ng; oi++)
 		{
 			size_t i = order[oi];
-			int64_t k0, k1;
+			int64_t k[GG_PLAN_MAX_GROUP_COLS];
 
-			plan_keys_of(R, (long long) rows[i * rowsz], &k0,
-				     &k1);
-			std::memcpy(w, &k0, 8);
-			std::memcpy(w + 8, &k1, 8);
-			w += 16;
+			plan_keys_of(R, (long long) rows[i * rowsz], k);
+			std::memcpy(w, k, keyb);
+			w += keyb;
 			for (const PlanResolved::OutAgg &O : R->outs)
 			{
 				const unsigned long long *v =
@@ -1705,6 +1822,7 @@ plan_topk_device(Engine &e, Pipeline *p, const PlanResolved *R,
 	K.limit = (int) limit;
 	K.ngroup = R->out_ngroup;
 	K.gp = plan_out_pack(R);
+	K.kn = R->gn.k;
 	for (int o = 0; o < R->norder; o++)
 		K.ord[o] = R->ord[o];
 
@@ -1786,7 +1904,8 @@ plan_bake(Engine &e, Pipeline *p, PlanResolved *R,
 			R->dev, R->dev.gnulls[0] != nullptr,
 			R->dev.gnulls[1] != nullptr, &R->rtc_baked,
 			codes.data(), (int) ng, fastok,
-			R->where0 ? &R->wh : nullptr);
+			R->where0 ? &R->wh : nullptr,
+			R->has_gn ? &R->gn : nullptr);
 
 		R->bake_tried = true;
 		if (rs == GG_OK)
@@ -1942,7 +2061,7 @@ exec_plan(Pipeline *p, void *arena, size_t bytes, size_t *written)
 		return fail(GG_ENOMEM, "plan scratch");
 	R->dev.err = derr;
 	GG_HIP(hipMemsetAsync(derr, 0, 8, e.stream));
-	if (R->dev.gp.packed)
+	if (R->dev.gp.packed || R->has_gn)
 		GG_TRY(plan_group_pack(e, p, R));
 	R->rg.gp = R->dev.gp;
 

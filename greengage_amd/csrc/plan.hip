@@ -483,6 +483,28 @@ __device__ static inline const PlanWhereDev &pl_where_arg(const PlWhere &W)
 	return W.w;
 }
 
+/* A plan with three or four group columns (engine_abi.h gg_plan_groups).  It
+ * is a fallback-tier plan like one with clauses and takes the same road: ONE
+ * more instantiation, the most general one, whose extra argument carries the
+ * clauses (none = a zeroed block, which passes every row) and, behind them,
+ * the group block.  No new read of P, and no existing kernel's argument
+ * block changes. */
+struct PlWhereN
+{
+	PlanWhereDev w;
+	PlanGroupNDev gn;
+};
+
+__device__ static inline const PlanWhereDev &pl_where_arg(const PlWhereN &W)
+{
+	return W.w;
+}
+
+__device__ static inline const PlanGroupNDev &pl_groupn_arg(const PlWhereN &W)
+{
+	return W.gn;
+}
+
 /* the post-join clauses of W, once per row that survived preds and joins.
  * Columns are read at the row their source names.  The test for a
  * NULL-extended source (pl_src_null, r == PL_NOROW) comes AHEAD of every
@@ -779,6 +801,37 @@ pl_group_code(const PlanDev &P, int64_t i, const PlRow<PL> &R)
 	    (P.gnulls[0] && P.gnulls[0][i0]))
 		return GG_PLAN_NULL_KEY;
 	return pl_ld<0>(P.gcol[0], P.gwidth[0], i0);
+}
+
+/* GP = 2: the code of G = N.k.n >= 3 packed fields (plan_dev.h PlanKeysN),
+ * field g = e_g << shift[g], e_g as in the packed pair and in the same
+ * unsigned arithmetic; the widths sum to <= 62, so the code is non-negative.
+ * Columns 0 and 1 are P's, columns 2 and 3 the block's. */
+template <int PL>
+__device__ static inline long long
+pl_group_code_n(const PlanDev &P, const PlanGroupNDev &N, int64_t i,
+		const PlRow<PL> &R)
+{
+	unsigned long long code = 0;
+
+	for (int g = 0; g < N.k.n && g < PL_MAX_GCOLS; g++)
+	{
+		const PlanGroupCol C = plan_group_col(P, N, g);
+		unsigned long long e = 0;
+
+		/* the NULL-extended source is tested ahead of every address
+		 * computation, the flag load included */
+		if (!pl_src_null<PL>(R, C.src))
+		{
+			const int64_t ig = pl_ix<PL>(R, C.src, i);
+
+			if (!(C.nulls && C.nulls[ig]))
+				e = (unsigned long long) pl_ld<0>(C.col, C.width, ig)
+					- (unsigned long long) N.k.gmin[g] + 1ull;
+		}
+		code |= e << N.k.shift[g];
+	}
+	return (long long) code;
 }
 
 /* strict-transition aggregate input (nodeAgg.c:413).  MM = the plan
@@ -1083,7 +1136,12 @@ void k_plan_scan_agg(PlanDev P, PlFilters<FL> F, Where... W)
 
 		if constexpr (FL)
 			fm = pl_row_filters<PL>(F.f, i, R);
-		long long code = pl_group_code<PL, GP>(P, i, R);
+		long long code;
+
+		if constexpr (GP == 2)
+			code = pl_group_code_n<PL>(P, pl_groupn_arg(W...), i, R);
+		else
+			code = pl_group_code<PL, GP>(P, i, R);
 		int ls = -1;
 		uint32_t pos = (uint32_t) gg_hashint8(code) & (LSLOTS - 1);
 
@@ -1208,8 +1266,9 @@ static void pl_launch(hipStream_t s, const PlanDev &p)
  * accumulator's kind), PL = 2 (pl_joins_outer walks all four join kinds and
  * none) and FL = 1 (an empty `used` mask evaluates nothing).  GP stays a
  * flag: the packed code is not a superset of the others. */
-static_assert(sizeof(PlanDev) + sizeof(PlFilters<1>) + sizeof(PlWhere) <=
-	      4096, "the interpreted kernel's arguments fit a kernarg segment");
+static_assert(sizeof(PlanDev) + sizeof(PlFilters<1>) + sizeof(PlWhereN) <=
+	      4096 && sizeof(PlWhereN) >= sizeof(PlWhere),
+	      "the interpreted kernel's arguments fit a kernarg segment");
 
 template <int GP>
 static void pl_launch_where(hipStream_t s, const PlanDev &p,
@@ -1219,6 +1278,21 @@ static void pl_launch_where(hipStream_t s, const PlanDev &p,
 
 	W.w = w;
 	hipLaunchKernelGGL((k_plan_scan_agg<0, 1, 2, GP, 1, PlWhere>),
+			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p,
+			   pl_filters_arg<1>(p), W);
+}
+
+/* ... and a plan with three or four group columns, with or without clauses:
+ * GP = 2 on the same general flags (see PlWhereN) */
+static void pl_launch_groupn(hipStream_t s, const PlanDev &p,
+			     const PlanWhereDev *w, const PlanGroupNDev &gn)
+{
+	PlWhereN W = {};
+
+	if (w)
+		W.w = *w;
+	W.gn = gn;
+	hipLaunchKernelGGL((k_plan_scan_agg<0, 1, 2, 2, 1, PlWhereN>),
 			   dim3(pl_grid(p.n)), dim3(PL_THREADS), 0, s, p,
 			   pl_filters_arg<1>(p), W);
 }
@@ -1267,8 +1341,13 @@ static_assert(pl_pinned<0, 0, 0, 0, 0>() && pl_pinned<1, 1, 2, 1, 1>() &&
 	      "k_plan_scan_agg launcher table: decode and encode disagree");
 
 hipError_t launch_plan_scan_agg(hipStream_t s, const PlanDev &p,
-				const PlanWhereDev *w)
+				const PlanWhereDev *w, const PlanGroupNDev *gn)
 {
+	if (gn)
+	{
+		pl_launch_groupn(s, p, w, *gn);
+		return hipGetLastError();
+	}
 	if (w)
 	{
 		if (p.ngroup == 2 && p.gp.packed)

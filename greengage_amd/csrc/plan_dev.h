@@ -28,13 +28,13 @@ typedef signed char int8_t;
 #include "../../include/engine_abi.h"
 #include "../../include/gg_pg_hash.h"
 /* How many of the trailing blocks PlanDev carries: 0 = it ends after `pl`,
- * 1 = `gp` follows, 2 = `gp` and `fl`, 3 = `gp`, `fl` and `wh`.  The host and
- * plan.hip always see 2.  A generated program is compiled at the lowest level
+ * 1 = `gp` follows, 2 = `gp` and `fl`, 3 = `gp`, `fl` and `wh`, 4 = those and
+ * `gn`.  The host and plan.hip always see 2.  A generated program is compiled at the lowest level
  * that holds what its plan reads, and launched with exactly that many bytes
  * (plan_rtc.cpp plan_arg_bytes): a plan without a packed group pair, an
  * aggregate filter or WHERE clauses keeps the argument block, and with it
- * the binary, it always had.  Level 3 exists in generated programs only (see
- * PlanWhereDev). */
+ * the binary, it always had.  Levels 3 and 4 exist in generated programs only
+ * (see PlanWhereDev and PlanGroupNDev). */
 #define PLAN_DEV_TAIL 2
 #endif
 
@@ -184,6 +184,46 @@ struct PlanWhereDev
 	int8_t nscan;
 };
 
+/* Three or four group columns (engine_abi.h gg_plan_groups), packed into one
+ * code of G fields, field 0 most significant:
+ *   code = e0 << shift[0] | e1 << shift[1] | ... | e(G-1),
+ * e_g as in PlanGroupPackDev, shift[g] = the summed widths of the fields
+ * behind field g (shift[G-1] = 0).  PlanKeysN is all a decoder needs
+ * (plan_keys.h); n = 0 says "not such a plan", and the code is then read by
+ * PlanGroupPackDev / ngroup as ever. */
+#define PL_MAX_GCOLS 4		/* GG_PLAN_MAX_GROUP_COLS */
+
+struct PlanKeysN
+{
+	int n;			/* G: 3 or 4, or 0 */
+	int shift[PL_MAX_GCOLS];
+	int64_t gmin[PL_MAX_GCOLS];
+};
+
+/* What a G >= 3 plan adds to the scan: group columns 2 and 3 (columns 0 and 1
+ * stay PlanDev.gcol / gnulls / gwidth / pl.gsrc) and the code's parameters,
+ * filled at the plan's first execute.
+ *
+ * Like PlanWhereDev, and for the same reasons, the block is NOT a member of
+ * the host's PlanDev: sizeof(PlanDev) and every offset in it stay what they
+ * were, no existing plan's argument block or program changes, and the
+ * interpreted kernel's arguments stay inside the 4 KiB a launch may pass.
+ * It rides BEHIND `wh`: a generated program of a G >= 3 plan is compiled at
+ * PLAN_DEV_TAIL 4, whose PlanDev declares `wh` and then `gn`, and
+ * plan_rtc_launch lays PlanWhereDev (all zero for a plan without clauses,
+ * which the program then never reads) and this block directly behind the
+ * host PlanDev's bytes (plan_rtc.cpp PlanDevGroupN).  The interpreted kernel
+ * gets it in the same argument that carries its clauses (plan.hip
+ * PlWhereN). */
+struct PlanGroupNDev
+{
+	const void *gcol[PL_MAX_GCOLS - 2];
+	const uint8_t *gnulls[PL_MAX_GCOLS - 2];
+	int gwidth[PL_MAX_GCOLS - 2];
+	int8_t gsrc[PL_MAX_GCOLS - 2];
+	PlanKeysN k;
+};
+
 struct PlanDev
 {
 	int64_t n;
@@ -207,6 +247,9 @@ struct PlanDev
 #endif
 #if PLAN_DEV_TAIL >= 3
 	PlanWhereDev wh;
+#endif
+#if PLAN_DEV_TAIL >= 4
+	PlanGroupNDev gn;
 #endif
 };
 

@@ -168,6 +168,7 @@ struct Gen
 	bool payload;		/* the plan holds an INNER or LEFT join: rows
 				 * carry the build-row indices r0, r1 */
 	const PlanWhereDev *W;	/* scope-0 WHERE clauses, or nullptr */
+	const PlanGroupNDev *N;	/* three or four group columns, or nullptr */
 };
 
 /* what a launch passes for a plan with WHERE clauses */
@@ -180,6 +181,20 @@ struct PlanDevWhere
 static_assert(offsetof(PlanDevWhere, wh) == sizeof(PlanDev) &&
 	      sizeof(PlanDevWhere) == sizeof(PlanDev) + sizeof(PlanWhereDev),
 	      "PlanWhereDev follows PlanDev's bytes without padding");
+
+/* ... and for a plan with three or four group columns, with clauses or
+ * without (plan_dev.h PlanGroupNDev: the block rides behind `wh`) */
+struct PlanDevGroupN
+{
+	PlanDev p;
+	PlanWhereDev wh;
+	PlanGroupNDev gn;
+};
+
+static_assert(offsetof(PlanDevGroupN, gn) == sizeof(PlanDevWhere) &&
+	      sizeof(PlanDevGroupN) == sizeof(PlanDevWhere) +
+	      sizeof(PlanGroupNDev),
+	      "PlanGroupNDev follows PlanWhereDev's bytes without padding");
 
 /* the plan has clauses evaluated after the joins */
 static bool where_post(const Gen &G)
@@ -224,9 +239,11 @@ static bool filter_args(const PlanDev &D)
 	return D.fl.used != 0;
 }
 
-static size_t plan_arg_bytes(const PlanDev &D, const PlanWhereDev *W)
+static size_t plan_arg_bytes(const PlanDev &D, const PlanWhereDev *W,
+			     const PlanGroupNDev *N)
 {
-	return W ? sizeof(PlanDevWhere) : filter_args(D) ? sizeof(PlanDev)
+	return N ? sizeof(PlanDevGroupN)
+		: W ? sizeof(PlanDevWhere) : filter_args(D) ? sizeof(PlanDev)
 		: packed_args(D) ? offsetof(PlanDev, fl) : offsetof(PlanDev, gp);
 }
 
@@ -238,9 +255,10 @@ static std::string ix_of(int src)
 }
 
 /* the tail level (plan_dev.h PLAN_DEV_TAIL) of a plan's program */
-static int plan_dev_tail(const PlanDev &D, const PlanWhereDev *W)
+static int plan_dev_tail(const PlanDev &D, const PlanWhereDev *W,
+			 const PlanGroupNDev *N)
 {
-	return W ? 3 : filter_args(D) ? 2 : packed_args(D) ? 1 : 0;
+	return N ? 4 : W ? 3 : filter_args(D) ? 2 : packed_args(D) ? 1 : 0;
 }
 
 /* the shared header behind its #defines, layout guards, tunables and the
@@ -248,7 +266,7 @@ static int plan_dev_tail(const PlanDev &D, const PlanWhereDev *W)
 static void emit_prelude(std::string &s, const Gen &G)
 {
 	const PlanDev &D = G.D;
-	const int tail = plan_dev_tail(D, G.W);
+	const int tail = plan_dev_tail(D, G.W, G.N);
 	/* host clang and the amdgcn compiler must agree on every struct the
 	 * program's PlanDev holds; `tail` = the lowest level that holds it */
 #define GG_LAYOUT(T, tail) {#T, sizeof(T), tail}
@@ -261,7 +279,8 @@ static void emit_prelude(std::string &s, const Gen &G)
 		GG_LAYOUT(PlanPredDev, 0), GG_LAYOUT(PlanJoinDev, 0),
 		GG_LAYOUT(PlanAggDev, 0), GG_LAYOUT(PlanPayloadDev, 0),
 		GG_LAYOUT(PlanGroupPackDev, 1), GG_LAYOUT(PlanFilterDev, 2),
-		GG_LAYOUT(PlanAtomDev, 3), GG_LAYOUT(PlanWhereDev, 3)};
+		GG_LAYOUT(PlanAtomDev, 3), GG_LAYOUT(PlanWhereDev, 3),
+		GG_LAYOUT(PlanKeysN, 4), GG_LAYOUT(PlanGroupNDev, 4)};
 #undef GG_LAYOUT
 
 	/* no header can be included under hipRTC: engine_abi.h's bounds go in
@@ -283,7 +302,7 @@ static void emit_prelude(std::string &s, const Gen &G)
 			s += fmt("static_assert(sizeof(%s) == %zu, \"layout\");\n",
 				 l.name, l.size);
 	s += fmt("static_assert(sizeof(PlanDev) == %zu, \"layout\");\n",
-		 plan_arg_bytes(D, G.W));
+		 plan_arg_bytes(D, G.W, G.N));
 
 	/* baked variant: more replicas by default — the accumulator
 	 * array has only nbake slots, so per-word contention is higher
@@ -792,6 +811,10 @@ static void emit_loop_head(std::string &s, const Gen &G)
 		"(long long) ((const int32_t *) P.gcol[%d])[%s]",
 		"((const int64_t *) P.gcol[%d])[%s]"};
 	std::string gi[2] = {ix_of(D.pl.gsrc[0]), ix_of(D.pl.gsrc[1])};
+	static const char *const ldn[] = {
+		"(long long) ((const uint8_t *) %s)[%s]",
+		"(long long) ((const int32_t *) %s)[%s]",
+		"((const int64_t *) %s)[%s]"};
 
 	s += R"GG(
 	for (int64_t i = (int64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -824,7 +847,42 @@ static void emit_loop_head(std::string &s, const Gen &G)
 					   D.pl.gsrc[g] - 1, g, gi[g].c_str())
 			: fmt("!h%d", D.pl.gsrc[g] - 1);
 	}
-	if (packed_args(D))
+	if (G.N)
+	{
+		/* three or four packed fields (plan_dev.h PlanKeysN): e_g as in
+		 * the packed pair below; the load widths, NULL presence and the
+		 * shifts are baked, the minima stay arguments */
+		std::string code;
+
+		for (int g = 0; g < G.N->k.n; g++)
+		{
+			const PlanGroupCol C = plan_group_col(D, *G.N, g);
+			const int src = C.src, w = C.width;
+			/* columns 0 and 1: NULL presence as the caller baked it */
+			const bool hasn = g < 2 ? G.gnull[g] : C.nulls != nullptr;
+			const bool ls = left_src(D, src);
+			const std::string ix = ix_of(src),
+				col = g < 2 ? fmt("P.gcol[%d]", g)
+				: fmt("P.gn.gcol[%d]", g - 2),
+				nf = (g < 2 ? fmt("P.gnulls[%d]", g)
+				      : fmt("P.gn.gnulls[%d]", g - 2)) + "[" + ix + "]",
+				isnull = !ls ? nf
+				: hasn ? fmt("(!h%d || ", src - 1) + nf + ")"
+				: fmt("!h%d", src - 1);
+			std::string e = fmt(ldn[w == 1 ? 0 : w == 4 ? 1 : 2],
+					    col.c_str(), ix.c_str());
+
+			e = fmt("(unsigned long long) (%s) - (unsigned long long) "
+				"P.gn.k.gmin[%d] + 1ull", e.c_str(), g);
+			if (hasn || ls)
+				e = isnull + " ? 0ull : " + e;
+			s += fmt("\t\tunsigned long long e%d = %s;\n", g, e.c_str());
+			code += fmt("%s(e%d << %d)", g ? " | " : "", g,
+				    G.N->k.shift[g]);
+		}
+		s += "\t\tlong long code = (long long) (" + code + ");\n";
+	}
+	else if (packed_args(D))
 	{
 		/* packed pair (engine_abi.h gg_plan_desc.group_cols): e = 0
 		 * for NULL, else v - min + 1 in unsigned arithmetic; the
@@ -1159,7 +1217,8 @@ compile_and_load(const std::string &src, int nbake,
 gg_status
 plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 		 std::shared_ptr<void> *out, const long long *bake,
-		 int nbake, bool fast, const PlanWhereDev *W)
+		 int nbake, bool fast, const PlanWhereDev *W,
+		 const PlanGroupNDev *N)
 {
 	const char *dis = getenv("GG_PLAN_RTC");
 
@@ -1179,7 +1238,8 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 	for (int j = 0; j < D.njoins; j++)
 		if (gg_join_builds_map(D.pl.jkind[j]))
 			payload = true;
-	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt, payload, W};
+	Gen G{D, {has_gnull0, has_gnull1}, bake, nbake, fast, nt, payload, W,
+	      N && N->k.n >= 3 ? N : nullptr};
 	std::string s;
 
 	emit_prelude(s, G);
@@ -1214,15 +1274,21 @@ plan_rtc_compile(const PlanDev &D, bool has_gnull0, bool has_gnull1,
 
 gg_status
 plan_rtc_launch(hipStream_t s, const std::shared_ptr<void> &h,
-		const PlanDev &P, int grid, int block, const PlanWhereDev *W)
+		const PlanDev &P, int grid, int block, const PlanWhereDev *W,
+		const PlanGroupNDev *N)
 {
 	PlanRtc *rtc = (PlanRtc *) h.get();
-	size_t size = plan_arg_bytes(P, W);
-	PlanDevWhere A;
+	size_t size = plan_arg_bytes(P, W, N);
+	PlanDevGroupN A;
 
+	/* the leading bytes are those of PlanDevWhere, and of PlanDev */
 	A.p = P;
 	if (W)
 		A.wh = *W;
+	else if (N)
+		std::memset(&A.wh, 0, sizeof(A.wh));
+	if (N)
+		A.gn = *N;
 	void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A,
 			  HIP_LAUNCH_PARAM_BUFFER_SIZE, &size,
 			  HIP_LAUNCH_PARAM_END};

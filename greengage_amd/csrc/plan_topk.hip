@@ -54,14 +54,15 @@ size_t plan_topk_lds_bytes(int norder)
 	return (size_t) PL_TOPK_TILE * (8 * (2 * (size_t) norder + 1) + 2);
 }
 
-/* one word that orders the rows as (key0, key1) ascending does, NULL keys
+/* one word that orders the rows as (key0, key1, ...) ascending does, NULL keys
  * (GG_PLAN_NULL_KEY, the smallest int64 a key can be) first */
 __device__ static inline unsigned long long
 pl_tie_word(const PlanTopkDev &K, unsigned long long code)
 {
-	if (K.gp.packed)
+	if (K.gp.packed || K.kn.n >= 3)
 		/* e = 0 for NULL, else the offset from the column minimum
-		 * plus 1: the packed code is already monotone in both keys */
+		 * plus 1: the packed code, of two fields or of N with field 0
+		 * most significant, is already monotone in all its keys */
 		return code;
 	if (K.ngroup == 2)
 	{
@@ -92,9 +93,9 @@ pl_order_words(const PlanTopkDev &K, const PlanOrderEnt &E,
 
 	if (E.kind == PL_ORD_KEY)
 	{
-		int64_t k[2];
+		int64_t k[PL_MAX_GCOLS];
 
-		plan_keys_of(K.gp, K.ngroup, (long long) row[0], &k[0], &k[1]);
+		plan_keys_of(K.gp, K.kn, K.ngroup, (long long) row[0], k);
 		null = k[E.slot] == GG_PLAN_NULL_KEY;
 		v = (unsigned long long) k[E.slot] ^ PL_MSB;
 	}

@@ -179,13 +179,15 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
            partner; a NULL probe key survives.  probe_src k takes
            probe_key from the build table of the earlier INNER or
            LEFT join k-1 (0 = driving table).
-    group_cols: 0-2 columns of any accepted type (char1, int32,
+    group_cols: 0-4 columns of any accepted type (char1, int32,
            int64) and source.  Two char1 columns keep their fixed
-           code; any other pair is packed into one 64-bit code by
-           the columns' value ranges and must fit 62 bits
-           (plan_group_bits).  The ranges are resolved at the first
-           execute_plan, which raises EngineError status 5 for a
-           pair that does not fit.
+           code; any other pair, and every list of three or four,
+           is packed into one 64-bit code by the columns' value
+           ranges and must fit 62 bits (plan_group_bits,
+           plan_group_bits_n).  The ranges are resolved at the first
+           execute, which raises EngineError status 5 for columns
+           that do not fit.  The descriptor holds the first two
+           columns; build_plan_groups holds the others.
     aggs: ["count"] | ("count", col) | ("count_distinct", col) |
           ("sum", [(col, "id"|"sub100"|"add100"), ...]) |
           ("min", (col, mod)) | ("max", (col, mod)) |
@@ -252,8 +254,9 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
         d.joins[j].probe_key = spec["probe_key"].encode()
         d.joins[j].kind = jkinds[spec.get("kind", "semi")]
         d.joins[j].probe_src = spec.get("probe_src", 0)
-    d.ngroup = len(group_cols)
-    for g, c in enumerate(group_cols):
+    # columns 2 and 3 travel beside the descriptor (build_plan_groups)
+    d.ngroup = min(len(group_cols), 2)
+    for g, c in enumerate(group_cols[:2]):
         d.group_cols[g], d.group_src[g] = colref(c)
     d.naggs = len(aggs)
     kinds = []
@@ -334,6 +337,24 @@ def build_plan_desc(scan_table, preds=(), joins=(), group_cols=(),
     d.limit = limit
     d.est_groups = est_groups
     return d, kinds
+
+
+def build_plan_groups(group_cols=()):
+    """The gg_plan_groups (engine_abi.h) of a plan's group columns: columns
+    2 and 3, which travel beside the descriptor; ncols = 0 for a plan with at
+    most two.  Pure, like build_plan_desc, and takes its column references."""
+    if len(group_cols) > PLAN_MAX_GROUP_COLS:
+        raise ValueError(
+            f"a plan groups by at most {PLAN_MAX_GROUP_COLS} columns")
+    g = _PlanGroups()
+    rest = list(group_cols[2:])
+    g.ncols = len(rest)
+    for i, c in enumerate(rest):
+        if isinstance(c, str):
+            g.cols[i], g.src[i] = c.encode(), 0
+        else:
+            g.cols[i], g.src[i] = c[1].encode(), 1 + c[0]
+    return g
 
 
 def build_plan_where(joins=(), where=()):
@@ -539,6 +560,15 @@ def build_plan_having(aggs=(), having=()):
     return h
 
 
+PLAN_MAX_GROUP_COLS = 4
+
+
+class _PlanGroups(ctypes.Structure):
+    _fields_ = [("cols", ctypes.c_char_p * (PLAN_MAX_GROUP_COLS - 2)),
+                ("src", ctypes.c_int8 * (PLAN_MAX_GROUP_COLS - 2)),
+                ("ncols", ctypes.c_int)]
+
+
 class KernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 48), ("launches", I64),
                 ("total_ms", ctypes.c_double), ("rows_in", I64),
@@ -613,6 +643,17 @@ def _load():
         ctypes.POINTER(_PlanHaving), ctypes.POINTER(I32)]
     lib.gg_engine_plan_having_size.argtypes = []
     lib.gg_engine_plan_having_size.restype = ctypes.c_size_t
+    lib.gg_engine_compile_plan_groups.restype = ctypes.c_int
+    lib.gg_engine_compile_plan_groups.argtypes = [
+        ctypes.POINTER(_PlanDesc), ctypes.POINTER(_PlanWhere),
+        ctypes.POINTER(_PlanHaving), ctypes.POINTER(_PlanGroups),
+        ctypes.POINTER(I32)]
+    lib.gg_engine_plan_groups_size.argtypes = []
+    lib.gg_engine_plan_groups_size.restype = ctypes.c_size_t
+    lib.gg_engine_plan_group_bits_n.restype = ctypes.c_int
+    lib.gg_engine_plan_group_bits_n.argtypes = [
+        ctypes.c_int, ctypes.POINTER(I64), ctypes.POINTER(I64),
+        ctypes.POINTER(ctypes.c_int)]
     lib.gg_engine_plan_desc_size.argtypes = []
     lib.gg_engine_plan_desc_size.restype = ctypes.c_size_t
     lib.gg_engine_plan_topk_tile.argtypes = []
@@ -762,6 +803,18 @@ def plan_group_bits(mn, mx):
     return rc, (bits[0], bits[1])
 
 
+def plan_group_bits_n(mn, mx):
+    """plan_group_bits for len(mn) = 1..4 group columns
+    (gg_engine_plan_group_bits_n): (status, (b0, ...)).  status 0 = the
+    columns fit the 62-bit budget, 5 (GG_ENOTSUP) = they do not, 1
+    (GG_EINVAL) = a column count outside 1..4.  Host arithmetic only."""
+    n = len(mn)
+    bits = (ctypes.c_int * max(n, 1))()
+    rc = lib().gg_engine_plan_group_bits_n(
+        n, (I64 * max(n, 1))(*mn), (I64 * max(n, 1))(*mx), bits)
+    return rc, tuple(bits[g] for g in range(n))
+
+
 def plan_topk_tile():
     """Rows per tile of the device top-k's tournament
     (gg_engine_plan_topk_tile): a constant of the library, no GPU needed."""
@@ -779,6 +832,7 @@ class Engine:
         self.segment_id = segment_id
         self._plan_kinds = {}   # plan handle -> descriptor agg kinds
         self._plan_limit = {}   # plan handle -> limit, where it has one
+        self._plan_ngroup = {}  # plan handle -> group columns, where > 2
 
     def shutdown(self):
         _check(lib().gg_engine_shutdown(), "engine_shutdown")
@@ -895,13 +949,23 @@ class Engine:
         arguments are build_plan_desc's, `where` (with the join specs'
         "where" keys) build_plan_where's and `having` build_plan_having's.
         A plan without a clause goes through gg_engine_compile_plan as
-        ever, one without a HAVING clause takes the calls it always took."""
+        ever, one without a HAVING clause takes the calls it always took,
+        and only one with three or four group columns (build_plan_groups)
+        goes through gg_engine_compile_plan_groups; its rows are read with
+        execute_plan_keys."""
         d, kinds = build_plan_desc(scan_table, preds, joins, group_cols,
                                    aggs, order_by, limit, est_groups)
         w = build_plan_where(joins, where)
         hv = build_plan_having(aggs, having)
+        gs = build_plan_groups(group_cols)
         h = I32()
-        if hv.nclauses:
+        if gs.ncols:
+            _check(lib().gg_engine_compile_plan_groups(
+                ctypes.byref(d), ctypes.byref(w) if w.nclauses else None,
+                ctypes.byref(hv) if hv.nclauses else None, ctypes.byref(gs),
+                ctypes.byref(h)), "compile_plan")
+            self._plan_ngroup[h.value] = d.ngroup + gs.ncols
+        elif hv.nclauses:
             _check(lib().gg_engine_compile_plan_having(
                 ctypes.byref(d), ctypes.byref(w) if w.nclauses else None,
                 ctypes.byref(hv), ctypes.byref(h)), "compile_plan")
@@ -923,13 +987,28 @@ class Engine:
         per descriptor aggregate: COUNT, COUNT(DISTINCT), SUM -> int,
         MIN/MAX -> int or None (SQL NULL), AVG -> (sum, count) for
         avg_str."""
+        if self._plan_ngroup.get(p, 0) > 2:
+            raise ValueError("a plan with more than two group columns is "
+                             "read with execute_plan_keys")
+        return [(k[0], k[1], v) for k, v in self._execute_plan_rows(
+            p, max_groups, 2)]
+
+    def execute_plan_keys(self, p, max_groups=1 << 16):
+        """One (keys, vals) per group of any plan, in arena order: keys is
+        the tuple of the plan's group keys (all four, or the two of
+        execute_plan; a NULL key is PLAN_NULL_KEY), vals as execute_plan's.
+        Without an order the rows are sorted by the key tuple."""
+        return self._execute_plan_rows(p, max_groups,
+                                       max(2, self._plan_ngroup.get(p, 0)))
+
+    def _execute_plan_rows(self, p, max_groups, nkeys):
         kinds = self._plan_kinds.get(p)
         nslots_guess = 8 if kinds is None else max(
             8, sum(2 if k == AGG_AVG else 1 for k in kinds))
         # a limited plan emits at most `limit` rows
         max_groups = min(max_groups, self._plan_limit.get(p, max_groups))
         raw = self.execute_raw(
-            p, 16 + max_groups * (16 + 16 * nslots_guess))
+            p, 16 + max_groups * (8 * nkeys + 16 * nslots_guess))
         ng = int.from_bytes(raw[0:8], "little", signed=True)
         nslots = int.from_bytes(raw[8:12], "little", signed=True)
         if kinds is None:
@@ -946,10 +1025,10 @@ class Engine:
             return lo, hi
 
         for _ in range(ng):
-            k0 = int.from_bytes(raw[off:off + 8], "little", signed=True)
-            k1 = int.from_bytes(raw[off + 8:off + 16], "little",
-                                signed=True)
-            off += 16
+            keys = tuple(int.from_bytes(raw[off + 8 * g:off + 8 * g + 8],
+                                        "little", signed=True)
+                         for g in range(nkeys))
+            off += 8 * nkeys
             vals = []
             for k in kinds:
                 lo, hi = slot()
@@ -961,7 +1040,7 @@ class Engine:
                     vals.append(((hi << 64) | lo, slot()[0]))
                 else:
                     vals.append((hi << 64) | lo)
-            groups.append((k0, k1, vals))
+            groups.append((keys, vals))
         return groups
 
     def set_nulls(self, table, col, nulls):

@@ -844,6 +844,8 @@ _Static_assert(sizeof(gg_plan_agg) == 2 * sizeof(int) + 3 * sizeof(char *) + 8,
  *   then n_groups rows, sorted by (key0, key1) ascending, or ordered and
  *   limited as the descriptor's order[] / limit say:
  *     int64 key0, int64 key1, then naggs x (uint64 lo, int64 hi)
+ *   (a plan with G = 3 or 4 group columns, gg_plan_groups below: ngroup is
+ *   G, every row carries G keys, and the order is over all of them)
  * naggs is the number of 16-byte result slots per row; slots follow
  * descriptor order:
  *   COUNT(*), COUNT(col), SUM   1 slot: a signed 128-bit value
@@ -1116,6 +1118,67 @@ int gg_engine_plan_topk_tile(void);
  * gg_engine_execute itself decides by. */
 gg_status gg_engine_plan_group_bits(const int64_t mn[2], const int64_t mx[2],
 				    int bits[2]);
+
+/* Three or four group columns: columns 2 and 3 are handed over BESIDE the
+ * descriptor, like gg_plan_where and gg_plan_having (gg_plan_desc keeps its
+ * layout and its ngroup <= 2 rule).  The plan then groups by G = 2 + ncols
+ * columns: desc->group_cols[0..1], then cols[0..ncols-1].  Types and sources
+ * are those of group_cols; NULL keys group separately per column, a column
+ * of a NULL-extended LEFT row reads as NULL, and group values of INT64_MIN
+ * or GG_PLAN_NULL_KEY stay unsupported.
+ *
+ * Code.  Every G >= 3 plan is packed by value ranges, char1 columns
+ * included, with b_g and e_g exactly as documented at
+ * gg_plan_desc.group_cols:
+ *   code = e0 || e1 || ... || e(G-1), field 0 most significant
+ * and is accepted iff the widths sum to at most 62
+ * (gg_engine_plan_group_bits_n).  The ranges are resolved at the first
+ * execute: an over-budget plan compiles, and every gg_engine_execute of it
+ * returns GG_ENOTSUP naming the widths.  With n_segments > 1 the ranges of
+ * all G columns are agreed across the segments, so all proceed or all
+ * refuse.  The code is monotone in (key0 .. key(G-1)) with NULL first.
+ *
+ * Group table.  est_groups == 0: the two-column table, 2^19 slots and at most
+ * 2^18 groups; est_groups > 0 sizes and grows it as for any plan.
+ *
+ * Arena.  The header's ngroup field is G, and every row carries G int64 keys
+ * (not two) ahead of its slots.  Without an order the rows are sorted by
+ * (key0 .. key(G-1)) ascending as raw int64; the same tuple breaks ties under
+ * an order.  A gg_plan_order entry with what = 0 may name index < G.
+ * HAVING, LIMIT and ORDER BY compose unchanged.  Plans with G <= 2 keep
+ * their arena byte for byte.
+ *
+ * groups == NULL or ncols == 0 is gg_engine_compile_plan_having exactly:
+ * same validation, same kernels, same generated programs, no new stat rows.
+ * Errors: ncols outside [0, 2] is GG_ENOTSUP; ncols > 0 with desc->ngroup
+ * != 2 is GG_EINVAL; a missing column, or a source naming a SEMI or ANTI
+ * join or a join >= njoins, is GG_EINVAL; a COUNT(DISTINCT) aggregate with
+ * ncols > 0 is GG_ENOTSUP (the inner code would need a fifth field).
+ * Stat rows: a packed G >= 3 execute counts path_plan_group_packed and
+ * path_plan_group_packed_n. */
+#define GG_PLAN_MAX_GROUP_COLS 4
+typedef struct gg_plan_groups		/* group columns 2 and 3 */
+{
+	const char *cols[GG_PLAN_MAX_GROUP_COLS - 2];
+	int8_t src[GG_PLAN_MAX_GROUP_COLS - 2];	/* column sources rule */
+	int ncols;				/* 0, 1 or 2 */
+} gg_plan_groups;
+
+gg_status gg_engine_compile_plan_groups(const gg_plan_desc *desc,
+					const gg_plan_where *where,
+					const gg_plan_having *having,
+					const gg_plan_groups *groups,
+					gg_pipeline *out);
+
+/* sizeof(gg_plan_groups), for bindings; needs no GPU */
+size_t gg_engine_plan_groups_size(void);
+
+/* gg_engine_plan_group_bits for n columns, 1 <= n <= GG_PLAN_MAX_GROUP_COLS
+ * (GG_EINVAL otherwise): fills bits[0..n-1] and returns GG_OK iff they sum to
+ * at most 62, else GG_ENOTSUP.  For n = 2 it is gg_engine_plan_group_bits.
+ * Pure host arithmetic, and what gg_engine_execute decides by. */
+gg_status gg_engine_plan_group_bits_n(int n, const int64_t *mn,
+				      const int64_t *mx, int *bits);
 
 /* Attach a NULL-flag array (1 byte per row, nonzero = NULL) to a
  * registered column — the nullable-scan surface (AO null bitmaps land

@@ -49,6 +49,12 @@
  *   wh     Q1 shape with a dense INNER join and WHERE clauses: a scan clause
  *          (disc in a range OR qty <= tax) and a post-join clause over a
  *          nullable payload column; generic + baked fast tier
+ *   gc3    Q1 shape grouped by three packed columns (char1, int32, int64)
+ *          of the driving table; generic + baked fast tier
+ *   gc4    Q1 shape with a dense LEFT join, grouped by four packed columns:
+ *          a char1 and a nullable int64 of the driving table, an int32
+ *          payload column with a NULL array and a char1 payload column;
+ *          generic + baked 2-word
  *   all    every shape above, DUMPFILE used as a prefix: <prefix><shape>.cu
  * Exit status is non-zero when a variant fails to COMPILE (a module
  * load / function lookup failure without a GPU is not a failure). */
@@ -260,6 +266,7 @@ dump_shape(const char *shape, const char *file)
 	int nbake = 0;
 	PlanDev D{};
 	PlanWhereDev W{};
+	PlanGroupNDev N{};
 	std::shared_ptr<void> out;
 
 	setenv("GG_PLAN_RTC_DUMP", file, 1);
@@ -471,6 +478,54 @@ dump_shape(const char *shape, const char *file)
 		codes = q1codes;
 		nbake = 6;
 	}
+	else if (!std::strcmp(shape, "gc3"))
+	{
+		/* fields of 9, 20 and 30 bits */
+		static const long long codes3[3] = {
+			(67ll << 50) | (5ll << 30) | 12345, (1ll << 50) | 1,
+			(80ll << 50) | (1000000ll << 30)};
+
+		shape_q1(D, false);
+		D.gwidth[1] = 4;
+		N.gcol[0] = dummy + 200;
+		N.gwidth[0] = 8;
+		N.k.n = 3;
+		N.k.shift[0] = 50;
+		N.k.shift[1] = 30;
+		N.k.gmin[1] = -40;
+		N.k.gmin[2] = 1ll << 50;
+		codes = codes3;
+		nbake = 3;
+	}
+	else if (!std::strcmp(shape, "gc4"))
+	{
+		/* fields of 9, 30, 12 and 9 bits; columns 2 and 3 are payload
+		 * columns of the LEFT join, NULL on a row without a partner */
+		static const long long codes4[3] = {
+			(67ll << 51) | (77ll << 21) | (9ll << 9) | 66,
+			(67ll << 51) | (77ll << 21), 0};
+
+		shape_q1(D, false);
+		join_dense(set_join(D, 0, GG_JOIN_LEFT, 8));
+		D.gwidth[1] = 8;
+		D.gnulls[1] = (const uint8_t *) dummy + 192;
+		N.gcol[0] = dummy + 200;
+		N.gwidth[0] = 4;
+		N.gnulls[0] = (const uint8_t *) dummy + 208;
+		N.gsrc[0] = 1;
+		N.gcol[1] = dummy + 224;
+		N.gwidth[1] = 1;
+		N.gsrc[1] = 1;
+		N.k.n = 4;
+		N.k.shift[0] = 51;
+		N.k.shift[1] = 21;
+		N.k.shift[2] = 9;
+		N.k.gmin[1] = -(1ll << 28);
+		N.k.gmin[2] = 8035;
+		wide = true;
+		codes = codes4;
+		nbake = 3;
+	}
 	else if (!std::strcmp(shape, "lrepl"))
 	{
 		setenv("GG_PLAN_LREPL", "32", 1);
@@ -487,7 +542,9 @@ dump_shape(const char *shape, const char *file)
 
 	bool gn0 = D.gnulls[0] != nullptr, gn1 = D.gnulls[1] != nullptr;
 	const PlanWhereDev *Wp = W.nclauses ? &W : nullptr;
-	gg_status s1 = plan_rtc_compile(D, gn0, gn1, &out, nullptr, 0, false, Wp);
+	const PlanGroupNDev *Np = N.k.n ? &N : nullptr;
+	gg_status s1 = plan_rtc_compile(D, gn0, gn1, &out, nullptr, 0, false, Wp,
+					Np);
 	bool ok = compiled(s1);
 
 	if (!ok)
@@ -496,7 +553,7 @@ dump_shape(const char *shape, const char *file)
 	if (nbake)
 	{
 		gg_status s2 = plan_rtc_compile(D, gn0, gn1, &out, codes,
-						nbake, !wide, Wp);
+						nbake, !wide, Wp, Np);
 
 		if (!compiled(s2))
 		{
@@ -518,7 +575,7 @@ main(int argc, char **argv)
 	static const char *const all[] = {"q1", "q1w", "q6", "q1mm", "q1mmw",
 		"q6mm", "gn8", "g4", "join", "pnull", "gp", "lrepl", "q1f", "pvf",
 		"left", "lefth", "year", "yearl", "innh", "lsemi", "linner", "ll",
-		"lln", "wh"};
+		"lln", "wh", "gc3", "gc4"};
 	const char *file = argc > 1 ? argv[1] : "/tmp/rtc_dump.cu";
 	const char *shape = argc > 2 ? argv[2] : "q1";
 	bool ok = true;
